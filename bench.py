@@ -27,6 +27,8 @@ Secondary entries of the same JSON line (`extra_configs`, single GPU only, fewer
 --loader runs the HEADLINE workload from that iterator too (collate + pinning + H2D inside the timed loop).
 
 Rank 0 prints ONE JSON line and exits non-zero if the loss or the gradient norm of the timed updates is not finite.
+--dump-outputs DIR writes what the LAST timed update computed as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 `roofline` times the dominant kernel family with HIP events inside the library (s2t_prof_*, on the launch stream) during
 instrumented updates that directly follow the timed region (inside it the events themselves cost 12 % of the update;
 --no-roofline skips them); `cpu_baseline` times the CPU oracle (port of the reference path, verified against it) on the
@@ -128,6 +130,28 @@ def timed_updates(trainer, next_batch, steps, warmup, world, device):
         dt = float(tmax.item())
     enc_mean = sum(sum(l) / len(l) for l in enc_len) / max(len(enc_len), 1)
     return dt, frames, enc_mean, stats
+
+
+DUMP_SAMPLE = 1 << 22        # elements of each flat arena buffer --dump-outputs writes (16 MB of f32 apiece, 32 MB in all)
+DUMP_SEED = 1
+
+
+def dump_outputs(path, trainer, stats):
+    """--dump-outputs: what the last timed update handed its caller -- the reduced logging outputs and the gradient norm, one
+    float64 scalar per key -- and what it left in the arena: the f32 gradient and the updated f32 master weights, each as a fixed
+    seeded sample of DUMP_SAMPLE elements of the flat buffer (the same elements on every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in stats.items() if not k.startswith("_")}
+    arena = trainer.arena
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(arena.numel, min(DUMP_SAMPLE, arena.numel), replace=False))
+    ix = torch.from_numpy(idx).to(arena.grad.device)
+    out["grad_sample"] = arena.grad[ix].float().cpu().numpy()
+    out["master_sample"] = arena.master[ix].float().cpu().numpy()
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(out)
 
 
 # RCCL all-reduce bus bandwidth ASSUMED by the projection below (8 MI355X, xGMI: 7 links x ~153 GB/s per GPU; a ring / tree over all
@@ -587,7 +611,11 @@ def main():
                          "measured update would be 8 encoder layers, not 12.  --lr 5e-3 reproduces that collapsed regime.")
     ap.add_argument("--attn-2d", action="store_true", help="diagnostic (not the headline workload, which is --no-attn-2d as in "
                     "BASELINE.md): keep the two ConvAttention2D blocks of the default front end; skips the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed updates, write what the last one computed as DIR/<name>.npy (float32 / float64, under 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.attn_2d:
         args.cpu_baseline = False
 
@@ -632,6 +660,8 @@ def main():
     torch.cuda.synchronize()
     dt, frames_done, enc_mean, stats = timed_updates(trainer, next_batch, args.steps, args.warmup, world, device)
     frames_per_step = frames_done // args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, stats)       # before the roofline / dry-run updates move the arena on
 
     roof = None
     if args.roofline:

@@ -4,13 +4,12 @@ tests/golden/plugin_boundary.json was produced by tests/golden/make_plugin_fixtu
 `options.get_training_parser` -> `parse_args_and_arch` -> `tasks.setup_task` -> `task.build_model` / `build_criterion`
 (fairseq/options.py:81-196, fairseq/utils.py:344-359, fairseq_cli/train.py:43-75) with this package as the user directory.
 Here (no reference needed) the package's standalone registries are held to the same outcome: same names registered, same
-namespace after the arch function, same classes, same parameter inventory.  When /root/reference is present (the build
-container) the fixture is regenerated in a subprocess and must be identical.
+namespace after the arch function, same classes, same parameter inventory.  Regenerating the fixture needs the reference
+itself: `make_plugin_fixture.py --check` does it and must find it identical.
 """
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 import pytest
@@ -72,11 +71,3 @@ def test_standalone_flow_matches_the_fairseq_flow(case):
     assert len(model.state_dict()) == exp["n_state_keys"]
     assert (len(task.source_dictionary), len(task.target_dictionary)) == (exp["src_dict"], exp["tgt_dict"])
     assert list(model.max_positions()) == exp["max_positions"]
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/fairseq"), reason="the reference is only present in the build container")
-def test_fixture_regenerates_identically_through_the_reference_cli_flow():
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "golden", "make_plugin_fixture.py"), "--check"], env=env,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:]
