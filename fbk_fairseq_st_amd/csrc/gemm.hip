@@ -748,9 +748,11 @@ static int launch(const GemmArgs& a_in, hipStream_t st) {
     if ((size_t)BM * (BN * 4 + 16) > lds) lds = (size_t)BM * (BN * 4 + 16);   // epilogue staging of the f32 tile
     if (fast) {
         if constexpr (BM == 128 && BN == 128 && sizeof(TI) == 2 && sizeof(TO) == 4 && TA && TB) {
-            // weight-gradient products: two k-slices per workgroup, half the atomic traffic
+            // weight-gradient products: two k-slices per workgroup, half the atomic traffic.  Its epilogue applies alpha and
+            // accumulate only: a product with a bias, an activation, a residual or dropout stays on the kernels below
             const int nk_total2 = a.K / 64;
-            if (!a.mapC && nk_total2 >= 4 * a.splitk && (a.splitk == 1 || a.splitk % 2 == 0)) {
+            const bool plain = !a.bias && !a.residual && !a.aux && !a.aux_out && a.act == ACT_NONE && a.p_drop == 0.f;
+            if (plain && !a.mapC && nk_total2 >= 4 * a.splitk && (a.splitk == 1 || a.splitk % 2 == 0)) {
                 GemmArgs b = a;
                 b.splitk = a.splitk > 1 ? a.splitk / 2 : 1;                    // same wavefronts per CU: s slices of 4 waves -> s/2 of 8
                 static bool attr4 = false;

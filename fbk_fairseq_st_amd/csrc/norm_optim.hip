@@ -210,9 +210,10 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const T* __restrict__ d
 
 // Small M (decoder-sized activations, small batches): at most 64 workgroups x 16 waves, i.e. 3-4 rows per wave, and inside an update every
 // row is a round trip to lines the previous launch wrote: with one row of lookahead the launch was a chain of them (11-13 us for 3,000-4,000
-// rows against 4.5 us for the forward).  Here a wave requests ALL its rows of a pass (four) before it reduces the first; the rows stay
-// raw (16 bytes per operand and lane) until they are used, so the twelve vectors fit the 128-register budget of a 1,024-thread workgroup.
-// Same arithmetic per row, same row order per wave: bit-identical to ln_bwd_kernel.  bf16, D = 512 (8 elements per lane).
+// rows against 4.5 us for the forward).  Here a wave requests ALL its rows of a pass (three) before it reduces the first; the rows stay
+// raw (16 bytes per operand and lane) until they are used, so the nine vectors fit the 128-register budget of a 1,024-thread workgroup.
+// Same formulas per row, same row order per wave; agrees with ln_bwd_kernel to bf16 rounding of the f32 evaluation, not bit for bit
+// (tests/test_routes_gpu.py).  bf16, D = 512 (8 elements per lane).
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void ln_bwd_small_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,

@@ -489,8 +489,6 @@ int s2t_prof_enable(int on);
  *       "gemm256_min_tiles": fewest 192 / 256-row output tiles a product must have for the 256-wide kernel (0 = default = 160;
  *                  tools/gemm_gate_probe.py measures both sides of it);
  *       "gemm256_sched": 1 selects gemm256's second K-loop schedule (diagnostic twins only: -95 in the product library);
- *       "gemm4w": 1 sends gemm256's NT products to the four-wave partition of the same tile (gemm4w.hip: an experiment,
- *                  bit-identical results, default 0);
  *       "reserve_cus": 0..128 (default 0): the persistent one-workgroup-per-CU kernels (gemm256, wgrad_group) launch 256 - value
  *                  workgroups and plan their rounds for that many CUs -- what a data-parallel run sets while RCCL's kernels share
  *                  the chip with backward (trainer: --reserve-cus);
