@@ -1,5 +1,6 @@
-// Pieces of the big-tile bf16 GEMM kernel (gemm256.hip: eight waves of 128 x 64; the archived four-wave experiment tools/lab/gemm4w.hip used them too):
-// the LDS image constants, the transposed fragment read, the epilogue arithmetic of one output quad and the buffer-addressed accesses.
+// Pieces of the big-tile bf16 GEMM kernels (gemm256.hip: eight waves of 128 x 64; wgrad_group.hip: the grouped weight gradients):
+// the LDS image constants, the LDS-DMA and transposed fragment reads, the epilogue arithmetic of one output quad and the buffer-addressed
+// accesses.
 #pragma once
 #include "common.hpp"
 #include "gemm_epilogue.hpp"

@@ -17,15 +17,10 @@
 // The bias gradient rides on the A operand: one extra MFMA per A fragment against a ones operand, spread over the four wave columns.
 #include "common.hpp"
 #include "prof.hpp"
+#include "gemm_tile.hpp"
 #include "../../include/s2t_hip.h"
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-typedef short s16x4_w __attribute__((ext_vector_type(4)));
-
 namespace {
-constexpr int HALF = 16384, BUF = 65536, BK = 64;
-
 struct Prob {
     const bf16* dY; const bf16* X; float* dW; float* db;
     int n_out, n_in, tokens, ldy, ldx, ldw, pad0, pad1;
@@ -35,24 +30,6 @@ struct Prob {
 struct Item { int prob, tm, tn, kt0, kt1, atomic; };
 
 __device__ uint4 g_zero_page[64];                                  // 1 KiB of zeros (device globals are zero-initialised)
-
-__device__ __forceinline__ int trswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ void glds16(const char* g, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((glb_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ u32x4 tr_frag(const char* img, int col, int s, int r16, int q) {
-    u32x4 f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int row = 32 * s + 8 * q + 4 * h + (r16 >> 2);
-        const int ch = (col >> 3) + ((r16 & 3) >> 1);
-        const char* a = img + row * 256 + ((ch ^ trswz(row)) << 4) + ((r16 & 1) << 3);
-        const s16x4_w v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_w*)a);
-        const u32x2 w = __builtin_bit_cast(u32x2, v);
-        f[2 * h] = w[0]; f[2 * h + 1] = w[1];
-    }
-    return f;
-}
 }  // namespace
 
 // 8 waves = 2 (M) x 4 (N).  Tile rows [128 h, 128 h + 128) form A half-tile h, wave row wr owns rows 64 wr .. 64 wr + 63 of each;

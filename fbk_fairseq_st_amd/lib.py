@@ -159,11 +159,9 @@ class DecodeDesc(ctypes.Structure):
 _lib = None
 
 
-def build(verbose=False, twins=False):
-    """Compile csrc/*.hip for gfx950 into libs2t_hip.so (hipcc cross-compiles without a GPU), then the CPython binding of its C ABI.
-    twins=True also builds the two diagnostic libraries of the store-data hazard reproducer (tests/test_kernels_gpu.py, marked slow:
-    S2T_SLOW=1); the product build does not depend on them."""
-    cmd = ["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 4)), "all"] + (["twins"] if twins else [])
+def build(verbose=False):
+    """Compile csrc/*.hip for gfx950 into libs2t_hip.so (hipcc cross-compiles without a GPU), then the CPython binding of its C ABI."""
+    cmd = ["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 4)), "all"]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if res.returncode != 0:
         raise RuntimeError("building libs2t_hip.so failed:\n" + res.stdout[-4000:])

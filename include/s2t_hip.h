@@ -488,7 +488,6 @@ int s2t_prof_enable(int on);
  *       "attn_v2_min_tq": shortest query block taken by the second-generation attention kernels (default 16);
  *       "gemm256_min_tiles": fewest 192 / 256-row output tiles a product must have for the 256-wide kernel (0 = default = 160;
  *                  tools/gemm_gate_probe.py measures both sides of it);
- *       "gemm256_sched": 1 selects gemm256's second K-loop schedule (diagnostic twins only: -95 in the product library);
  *       "reserve_cus": 0..128 (default 0): the persistent one-workgroup-per-CU kernels (gemm256, wgrad_group) launch 256 - value
  *                  workgroups and plan their rounds for that many CUs -- what a data-parallel run sets while RCCL's kernels share
  *                  the chip with backward (trainer: --reserve-cus);
@@ -502,9 +501,6 @@ int s2t_prof_enable(int on);
  *                  of keeping two in flight; bit-identical results (tools/gemm_deep_check.py); 0 restores the two-set loop;
  *       "ln_small" (default 1): the bf16, D = 512 LayerNorm backward of activations below 8,192 rows requests a wave's rows three at a
  *                  time instead of one ahead (same formulas; results agree with the other kernel to bf16 rounding); 0 restores it;
- *       "attn_bwd_fused" (default 0): 1 sends the bf16, d = 64, plain-softmax attention backward with 128 <= Tk <= 384 and Tq >= 128 to
- *                  the one-kernel form (attention.hip: attn_bwd_fused_kernel; same results within bf16 rounding, measured no faster:
- *                  profiles/r06_attn_bwd_fused.txt);
  *       "decode_stop_after": diagnostic, ends s2t_decode_step after that many launches (0 = off);
  * returns the previous value, or S2T_EINVAL (-22) for an unknown key or a value out of range. */
 int s2t_set_option(const char* key, int value);

@@ -69,6 +69,7 @@ def test_generated_cpython_binding_matches_the_ctypes_binding():
     for name, args in calls:
         assert getattr(fast, name)(*args) == getattr(raw, name)(*args), name
     assert fast.s2t_set_option(b"no_such_option", 1) == -22 and fast.s2t_build_info() == L.load().s2t_build_info()
+    assert fast.s2t_set_option(b"gemm256_sched", 1) == -22 and fast.s2t_set_option(b"attn_bwd_fused", 1) == -22   # removed options
     import pytest
     with pytest.raises(TypeError):
         fast.s2t_abi_version(1)

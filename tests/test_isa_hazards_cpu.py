@@ -3,8 +3,8 @@
 The data registers of a wide LDS write (ds_write_b96 / b128) or a 16-byte vector store are read out over several cycles after the
 instruction has issued; hipcc pads two wait states after a wide buffer store and none after a wide LDS write, and in the gemm256
 epilogue -- 16 steps of ds_write_b128 / ds_read_b128 / buffer_store_dwordx4 per tile, with the SIMD partner's memory instructions in
-the same queues -- a VALU write two or three instructions behind such an instruction ended up in the stored tile (round 4:
-tests/test_kernels_gpu.py::test_gemm256_store_data_hazard_twins, tools/gemm_sched_diff.py).  The epilogue therefore closes every
+the same queues -- a VALU write two or three instructions behind such an instruction ended up in the stored tile (round 4, found
+with a diagnostic schedule in which both waves of a SIMD stored at once).  The epilogue therefore closes every
 step with an asm that READS those registers and waits; this test holds the compiler's output to it: in every instantiation of the
 kernel no VALU instruction writes the data registers of a wide store within MIN_STATES issue slots (tools/isa_store_hazards.py)."""
 import os

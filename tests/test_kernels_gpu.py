@@ -790,7 +790,7 @@ TURN_SHAPES = [(24000, 384, 192), (24000, 512, 512), (24000, 1536, 512), (24000,
 
 @pytest.mark.parametrize("M,N,K_", TURN_SHAPES)
 def test_gemm256_epilogues_against_the_128_wide_route_and_themselves(M, N, K_):
-    """tools/gemm_turn_check.py as a test: every epilogue variant of gemm256 (stores leave in a lane order turned through wave-private
+    """Every epilogue variant of gemm256 (stores leave in a lane order turned through wave-private
     LDS slots, masked epilogue per quad, unmasked one straight-line) on ten shapes, six launches each.  The 128-wide route (gemm.hip)
     runs the same MFMA instruction over K in the same order and the same epilogue arithmetic (gemm_epilogue.hpp), so the two routes
     must agree BIT FOR BIT, and every repeated launch must reproduce the first one (a store path that races shows up as a few
@@ -844,53 +844,6 @@ def test_gemm256_product_epilogues_soak_against_the_128_wide_route():
     import gemm_soak
     bad, total = gemm_soak.soak(200, shapes=[(24000, 2048, 512), (24000, 512, 512)], verbose=False)
     assert total == 2 * 6 * 200 and bad == 0, "%d of %d launches differ from the 128-wide route" % (bad, total)
-
-
-@pytest.mark.slow
-def test_gemm256_store_data_hazard_twins():
-    """Round 3 left "wrong values when the two wave groups' epilogues overlap" unexplained; this is its reproducer.  `make twins` builds
-    gemm256 with a second K-loop schedule in which all eight waves -- both waves of every SIMD -- run their epilogues at the same
-    time (s2t_set_option "gemm256_sched" 1; not in the product library, whose schedule keeps one epilogue per SIMD at a time):
-      libs2t_hip_sched1_nohold.so   the epilogue as round 3 had it: hipcc re-uses a 16-byte store's data registers two instructions
-                                    after the store (the wait states the ISA asks for).  With the SIMD partner storing too, the
-                                    younger wave's stores leave with the NEXT step's f32 intermediates in their first dwords, lanes
-                                    12-15 of every 16-lane row (the data beats read last; tools/gemm_sched_diff.py decodes it):
-                                    thousands of wrong values in nearly every launch of a masked or operand-reading epilogue.
-      libs2t_hip_sched1.so          stores from a four-deep register ring that is untouched for three steps (the product's epilogue):
-                                    the raw-f32 garbage is gone; a residue of stale-but-valid values (same lanes, ~1e-5 of the
-                                    elements, a few launches in a hundred) remains in the operand-reading variants, i.e. a second
-                                    mechanism is still open -- which is why concurrent epilogues stay out of the product.
-    Asserted: the product library is bit-exact against the 128-wide route (test above); without the hold the hazard shows; the hold
-    removes at least three quarters of the differing launches.  Counts are printed."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "fbk_fairseq_st_amd")
-
-    def sums(lib, sched):
-        env = dict(os.environ)
-        if lib:
-            env["S2T_HIP_LIB"] = os.path.join(pkg, lib)
-            if not os.path.exists(env["S2T_HIP_LIB"]):
-                pytest.skip("diagnostic twins not built (make -C fbk_fairseq_st_amd/csrc twins; lib.build(twins=True))")
-        out = subprocess.run([sys.executable, os.path.join(root, "tools", "gemm_epilogue_sums.py"), str(sched)], env=env,
-                             capture_output=True, text=True, timeout=900)
-        assert out.returncode == 0, out.stderr[-2000:]
-        return [l for l in out.stdout.splitlines() if l.startswith("SUM ")]
-
-    want = sums(None, 0)
-    assert len(want) == 4 * 6 * 4
-    raw = sums("libs2t_hip_sched1_nohold.so", 1)
-    held = sums("libs2t_hip_sched1.so", 1)
-    n_raw = sum(a != b for a, b in zip(want, raw))
-    n_held = sum(a != b for a, b in zip(want, held))
-    plain = [k for k, (a, b) in enumerate(zip(want, held)) if a != b and a.split()[4] in ("0", "4")]
-    print("MEASURED store-data hazard (both waves of a SIMD in their epilogues): %d of %d launches differ from the product library "
-          "without the register hold, %d with it" % (n_raw, len(want), n_held))
-    assert not plain, "the plain epilogues (no mask, no operand stream) must be exact under either arrangement"
-    if n_raw == 0:
-        pytest.xfail("the hazard did not show on this box")
-    assert n_held * 4 <= n_raw, (n_held, n_raw)
 
 
 def test_gemm256_is_deterministic_under_load():
@@ -1268,31 +1221,3 @@ def test_dropout_fused_into_bn_apply_and_scattered_gemm_epilogue(dtype):
         assert torch.equal(o1, ref)
     else:                                                       # ... the epilogue scales the f32 accumulator (one rounding instead of two)
         assert rel_err(o1, ref) < 1e-2
-
-def test_attn_bwd_fused_matches_two_kernel_path():
-    """s2t_set_option "attn_bwd_fused" (default off: measured no faster, profiles/r06_attn_bwd_fused.txt): the one-kernel attention backward
-    for Tk <= 384 against the two-kernel path on the encoder's shape with dropout and ragged key lengths -- dV identical (the same
-    arithmetic in the same order), dK / dQ within 4e-3 of the largest element (bf16 operands, another order over the keys)."""
-    g = torch.Generator(device=DEV).manual_seed(5)
-    B, H, T = 3, 8, 375
-    D = 64 * H
-    qkv = (torch.randn(T, B, 3 * D, device=DEV, generator=g) * 0.7).to(torch.bfloat16)
-    q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
-    do = torch.randn(T, B, D, device=DEV, generator=g).to(torch.bfloat16)
-    kl = torch.tensor([375, 250, 131], dtype=torch.int32, device=DEV)
-    o, lse = K.attn_fwd(q, k, v, H, klen=kl, p_drop=0.1, seed=9)
-    res = []
-    try:
-        for fused in (0, 1):
-            K.set_option("attn_bwd_fused", fused)
-            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-            K.attn_bwd(q, k, v, o, do, lse, H, dq, dk, dv, klen=kl, p_drop=0.1, seed=9)
-            torch.cuda.synchronize()
-            res.append((dq.float(), dk.float(), dv.float()))
-    finally:
-        K.set_option("attn_bwd_fused", 0)
-    (q0, k0, v0), (q1, k1, v1) = res
-    assert torch.equal(v0, v1)
-    for a, b_ in ((q0, q1), (k0, k1)):
-        assert torch.isfinite(b_).all()
-        assert float((a - b_).abs().max()) <= 4e-3 * float(a.abs().max())

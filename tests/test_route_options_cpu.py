@@ -28,9 +28,10 @@ def header_keys():
     return set(re.findall(r'"(\w+)"\s*(?:/\s*"(?:\w+)")?\s*(?:\(|:)', block)) | set(re.findall(r'/ "(\w+)"', block))
 
 
-def test_option_parser_sees_the_known_keys():
-    keys = library_keys()
-    assert {"gemm256", "reserve_cus", "ln_small", "gemm_deep", "decode_stop_after"} <= keys and len(keys) >= 15, keys
+def test_option_parser_sees_exactly_the_known_keys():
+    assert library_keys() == {"gemm256", "attn_v1", "attn_v2_min_tq", "gemm256_min_tiles", "decode_stop_after", "reserve_cus",
+                              "gemm_f32_small_nt", "gemm_f32_small_kt", "gemm_f32_narrow", "gemm_small_nt", "gemm_small_kt",
+                              "gemm_deep", "ln_small"}, library_keys()
 
 
 def test_header_documents_exactly_the_library_keys():

@@ -480,26 +480,16 @@ def test_gemm256_relu_record_follows_reserve_cus():
     assert_close(da, ref, gd.accb + UBF * ref.abs(), "relu mask bwd reserve 16")
 
 
-def test_gemm256_sched_refused_in_product_library():
-    """gemm256_sched = 1 is a diagnostic schedule built only into the twins: the product library refuses a gemm256-shaped product with
-    S2THipError (-95) instead of returning data (gemm256.hip: `if (sched != 0) return S2T_ENOTSUP`); products that do not reach
-    gemm256 are unaffected"""
-    from fbk_fairseq_st_amd import lib as L
+def test_gemm256_takes_m24000_n512_k512():
+    """24,000 x 512 x 512 (250 tiles of 192 rows) runs as one gemm256_nt launch; fp64 bound.  (997 x 701 x 512 on gemm_nt_small:
+    test_gemm64_deep_prefetch_both_loops, test_gemm64_deep_epilogues)"""
     a, b = _operands("nt", 24000, 512, 512, BF)
-    small_a, small_b = _operands("nt", 997, 701, 512, BF)
-    g = Gemm(small_a, small_b, False, False)
-    with set_option("gemm256_sched", 1):
-        with pytest.raises(L.S2THipError) as e:
-            K.gemm(a, b)
-            torch.cuda.synchronize()
-        assert "error -95" in str(e.value), str(e.value)
-        with launches() as c:
-            out = K.gemm(small_a, small_b)
-        only(c, "gemm_nt_small")
-        assert_close(out, g.acc, g.accb + UBF * g.acc.abs(), "small product under gemm256_sched")
+    g = Gemm(a, b, False, False)
     with launches() as c:
-        K.gemm(a, b)
-    assert c["gemm256_nt"] == 1          # and the option's old value is back
+        out = K.gemm(a, b)
+    only(c, "gemm256_nt")
+    assert c["gemm256_nt"] == 1, c
+    assert_close(out, g.acc, g.accb + UBF * g.acc.abs(), "gemm256 24000 x 512 x 512")
 
 
 def test_gemm256_min_tiles_and_off_switch():
@@ -856,12 +846,11 @@ def test_attention_v2_min_tq_raised():
 
 @pytest.mark.parametrize("Tq", [127, 128])
 @pytest.mark.parametrize("Tk", [127, 128, 384, 385])
-def test_attention_bwd_fused_against_fp64(Tq, Tk):
-    """attn_bwd_fused = 1: attention.hip takes attn_bwd_fused_kernel for bf16, d = 64, no causal mask, 128 <= Tk <= 384 and Tq >= 128
-    (only Tq 128 with Tk 128 / 384 here); the others fall back to the two-kernel path.  Every case against fp64, ragged keys, and
-    the dropout adjoint identity on the fused route"""
+def test_attention_bwd_two_kernel_around_128_and_384_against_fp64(Tq, Tk):
+    """the default backward (bwd_launch) for bf16, d = 64, no causal mask at Tq / Tk = 127 / 128, where the second-generation dq2 /
+    dkv2 kernels' Tq >= 128 and Tk >= 128 gates flip, and at Tk = 384 / 385 around the encoder's 375 keys.  Every case against
+    fp64, ragged keys, and the dropout adjoint identity"""
     B, H = 3, 8
     klen = torch.tensor([Tk, Tk - 5, max(1, Tk // 3)], dtype=torch.int32)
-    with set_option("attn_bwd_fused", 1):
-        q, k, v, do, kl, ctx = attn_check(BF, H, B, Tq, Tk, klen, False, "fused Tq=%d Tk=%d" % (Tq, Tk))
-        attn_dropout_adjoint(q, k, v, do, kl, False, ctx, "fused Tq=%d Tk=%d" % (Tq, Tk))
+    q, k, v, do, kl, ctx = attn_check(BF, H, B, Tq, Tk, klen, False, "bwd Tq=%d Tk=%d" % (Tq, Tk))
+    attn_dropout_adjoint(q, k, v, do, kl, False, ctx, "bwd Tq=%d Tk=%d" % (Tq, Tk))
