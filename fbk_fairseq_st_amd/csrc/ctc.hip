@@ -680,3 +680,267 @@ extern "C" int s2t_ctc_loss(int dtype, const void* logits, const long long* targ
     S2T_LAUNCH_CHECK();
     return S2T_OK;
 }
+
+// ------------------------------------------------------------------ CTC loss for any transcript length and vocabulary size
+// s2t_ctc_loss_any: the same loss and gradient as s2t_ctc_loss without its two limits (S = 2L+1 <= 1024 states held in one wave's
+// registers, one f32 row of the vocabulary in LDS).  Three passes, all sized by the data rather than by the kernel:
+//   1. ctc_emit_any_kernel writes every row's emissions lp[t][s] = (logit[ext s] - lse) log2 e into BOTH la and lb (fully parallel);
+//   2. ctc_alphabeta_any_kernel, one workgroup per (utterance, direction), walks the frames and overwrites row t of its buffer in
+//      place with alpha_t (beta_t): the state vector lives in the workspace itself, so S has no upper bound.  Each step reads the
+//      previous row (just written by the workgroup: one barrier per step), the step's emissions from the row it overwrites, and
+//      keeps the conventions of ctc_alphabeta_kernel: log2 units, CTC_NEVER, every fourth step shifted by the maximum of the vector it
+//      starts from (one workgroup-wide maximum, so every wave subtracts the same offset), offsets summed in double, blanks never skip;
+//   3. ctc_grad_any_kernel, one workgroup per (t,b) row: frame maximum and sum over the states in strided loops, the softmax row
+//      written with 16-byte stores, then the posteriors subtracted per DISTINCT transcript label.  ctc_rep_any_kernel maps label k
+//      of the utterance (k = 0: blank, k >= 1: targets[k-1]) to its first occurrence rep[k], once per utterance; the gradient pass
+//      adds each state's posterior into an LDS slot of its label's first occurrence (CTC_ANY_ITEMS slots per sweep; longer
+//      transcripts take several sweeps) and rewrites only those columns.  The slots hold 2^-52 fixed point in u64: integer atomics
+//      add in any order to the same bits, so the gradient is deterministic (phase 2 reproduces phase 0 exactly).
+#define CTC_ANY_ROW(Lmax) (((long)2 * (Lmax) + 1 + 63) / 64 * 64)      // la / lb row stride: S rounded up to a multiple of 64
+#define CTC_ANY_REP(Lmax) (((long)(Lmax) + 1 + 63) / 64 * 64)          // rep row stride: the L+1 labels (blank first), likewise
+#define CTC_ANY_ITEMS 4096
+#define CTC_ANY_FIX 4503599627370496.0                                 // 2^52: fixed-point scale of the occupancies
+
+// column of extended position s (clamped into the row: a label outside [0, V) is the caller's error, never a read outside the row)
+__device__ __forceinline__ int ctc_any_col(const long long* tg, int s, int blank, int V) {
+    const long long c = (s & 1) ? tg[s >> 1] : (long long)blank;
+    return (int)min(max(c, 0ll), (long long)V - 1);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_emit_any_kernel(const T* __restrict__ logits, const float* __restrict__ lse,
+                                                           const long long* __restrict__ targets, const long long* __restrict__ tgt_len,
+                                                           const int* __restrict__ in_len, float* __restrict__ la, float* __restrict__ lb,
+                                                           int Tn, int B, int V, int ld, int Lmax, long Srow, int blank) {
+    const int t = blockIdx.x, b = blockIdx.y;
+    if (t >= min(in_len[b], Tn)) return;
+    const int S = 2 * min((int)tgt_len[b], Lmax) + 1;
+    const long row = (long)t * B + b;
+    const T* x = logits + row * ld;
+    const float ls = lse[row];
+    const long long* tg = targets + (long)b * Lmax;
+    const long o = ((long)b * Tn + t) * Srow;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        const float v = (to_f32(x[ctc_any_col(tg, s, blank, V)]) - ls) * 1.44269504088896f;
+        la[o + s] = v;
+        lb[o + s] = v;
+    }
+}
+
+__global__ __launch_bounds__(1024) void ctc_alphabeta_any_kernel(const long long* __restrict__ targets, const long long* __restrict__ tgt_len,
+                                                                 const int* __restrict__ in_len, float* __restrict__ la, float* __restrict__ lb,
+                                                                 float* __restrict__ nll, int Tn, int Lmax, long Srow, int blank) {
+    __shared__ float redm[16];
+    const int b = blockIdx.x, dir = blockIdx.y;
+    const int nt = blockDim.x, nw = nt >> 6, lane = threadIdx.x & 63;
+    const int L = min((int)tgt_len[b], Lmax), S = 2 * L + 1, Tb = min(in_len[b], Tn);
+    const long long* tg = targets + (long)b * Lmax;
+    float* base = (dir == 0 ? la : lb) + (long)b * Tn * Srow;
+    const int s_start = dir == 0 ? 0 : S - 1;          // the virtual state before the first step: delta(s = 0) / delta(s = S-1)
+    double offsum = 0.0;
+    for (int i = 0; i < Tb; ++i) {
+        const int t = dir == 0 ? i : Tb - 1 - i;
+        float* cur = base + (long)t * Srow;
+        const float* prv = base + (long)(i == 0 ? t : (dir == 0 ? t - 1 : t + 1)) * Srow;      // read only when i > 0
+        auto prev = [&](int s) -> float { return i == 0 ? (s == s_start ? 0.f : CTC_NEVER) : prv[s]; };
+        float sh = 0.f;
+        if ((i & 3) == 0) {
+            float loc = CTC_NEVER;
+            for (int s = threadIdx.x; s < S; s += nt) loc = fmaxf(loc, prev(s));
+            loc = wave_max(loc);
+            if (lane == 0) redm[threadIdx.x >> 6] = loc;
+            __syncthreads();
+            sh = redm[0];
+            for (int w = 1; w < nw; ++w) sh = fmaxf(sh, redm[w]);
+            sh = sh > CTC_NEVER_TEST ? sh : 0.f;                  // (nothing reachable: an infeasible alignment, nothing to shift)
+            offsum += (double)sh;
+        }
+#pragma unroll 4
+        for (int s = threadIdx.x; s < S; s += nt) {
+            const float e = cur[s] - sh;                           // this step's emission (ctc_emit_any_kernel), shifted
+            const float a0 = prev(s);
+            float n;
+            if (dir == 0) {
+                const float m1 = s >= 1 ? prev(s - 1) : CTC_NEVER;
+                if ((s & 1) == 0) n = l2ae2(a0, m1) + e;
+                else {
+                    const long long u = tg[s >> 1];
+                    const bool sk = s >= 3 && u != blank && u != tg[(s >> 1) - 1];
+                    n = l2ae3(a0, m1, sk ? prev(s - 2) : CTC_NEVER) + e;
+                }
+            } else {
+                const float m1 = s + 1 < S ? prev(s + 1) : CTC_NEVER;
+                if ((s & 1) == 0) n = l2ae2(a0, m1) + e;
+                else {
+                    const bool sk = s + 2 < S && tg[(s >> 1) + 1] != blank && tg[(s >> 1) + 1] != tg[s >> 1];
+                    n = l2ae3(a0, m1, sk ? prev(s + 2) : CTC_NEVER) + e;
+                }
+            }
+            cur[s] = n;
+        }
+        __syncthreads();                                           // row t complete before any thread reads it as the previous row
+    }
+    if (dir == 0 && threadIdx.x == 0) {
+        // log-likelihood = logaddexp(alpha[Tb-1][S-1], alpha[Tb-1][S-2])
+        float v = CTC_NEVER;
+        if (Tb > 0) {
+            const float* last = base + (long)(Tb - 1) * Srow;
+            if (S >= 2) v = l2ae2(v, last[S - 2]);
+            v = l2ae2(v, last[S - 1]);
+        }
+        nll[b] = (Tb > 0 && v > CTC_NEVER_TEST) ? (float)(-((double)v + offsum) * 0.693147180559945309) : INFINITY;
+    }
+}
+
+// rep[b][k] = first k' <= k whose label is label k's (k = 0: blank, k >= 1: targets[b][k-1]); one workgroup per utterance, earlier
+// labels compared through LDS tiles
+__global__ __launch_bounds__(1024) void ctc_rep_any_kernel(const long long* __restrict__ targets, const long long* __restrict__ tgt_len,
+                                                           int* __restrict__ rep, int Lmax, long Rrow, int blank) {
+    __shared__ long long tile[1024];
+    const int b = blockIdx.x, n = min((int)tgt_len[b], Lmax) + 1;
+    const long long* tg = targets + (long)b * Lmax;
+    auto label = [&](int k) -> long long { return k == 0 ? (long long)blank : tg[k - 1]; };
+    for (int k0 = 0; k0 < n; k0 += 1024) {
+        const int k = k0 + (int)threadIdx.x;
+        const long long lk = k < n ? label(k) : 0;
+        int r = k;
+        for (int j0 = 0; j0 <= k0; j0 += 1024) {
+            __syncthreads();
+            if (j0 + (int)threadIdx.x < n) tile[threadIdx.x] = label(j0 + threadIdx.x);
+            __syncthreads();
+            const int jn = min(1024, min(n, k) - j0);            // only labels before k
+            for (int j = 0; j < jn && r == k; ++j)
+                if (tile[j] == lk) r = j0 + j;
+        }
+        if (k < n) rep[(long)b * Rrow + k] = r;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_grad_any_kernel(const T* __restrict__ logits, const float* __restrict__ lse,
+                                                           const long long* __restrict__ targets, const long long* __restrict__ tgt_len,
+                                                           const int* __restrict__ in_len, const float* __restrict__ la,
+                                                           const float* __restrict__ lb, const int* __restrict__ rep,
+                                                           const float* __restrict__ nll, T* __restrict__ grad, int Tn, int B, int V,
+                                                           int ld, int Lmax, long Srow, long Rrow, int blank, float gscale,
+                                                           const float* __restrict__ gscale_dev) {
+    __shared__ unsigned long long occ[CTC_ANY_ITEMS];
+    __shared__ float red[4];
+    if (gscale_dev) gscale *= gscale_dev[0];
+    const int t = blockIdx.x, b = blockIdx.y;
+    const long row = (long)t * B + b;
+    T* g = grad + row * ld;
+    const bool live = t < min(in_len[b], Tn) && nll[b] < INFINITY;
+    if (!live) { for (int c = threadIdx.x; c < V; c += 256) g[c] = from_f32<T>(0.f); return; }
+    constexpr float L2E = 1.44269504088896f;
+    const float ls = lse[row];
+    const T* x = logits + row * ld;
+    const int L = min((int)tgt_len[b], Lmax), S = 2 * L + 1;
+    const long long* tg = targets + (long)b * Lmax;
+    const float* ra = la + ((long)b * Tn + t) * Srow;
+    const float* rb = lb + ((long)b * Tn + t) * Srow;
+    auto weight = [&](int s) -> float {                        // la + lb - lp (log2 units), -inf where unreachable
+        const float lab = ra[s] + rb[s];
+        return lab > CTC_NEVER_TEST ? lab - (to_f32(x[ctc_any_col(tg, s, blank, V)]) - ls) * L2E : -INFINITY;
+    };
+    float mx = -INFINITY;
+    for (int s = threadIdx.x; s < S; s += 256) mx = fmaxf(mx, weight(s));
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sm = 0.f;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        const float w = weight(s);
+        if (w > -INFINITY) sm += __builtin_amdgcn_exp2f(w - mx);
+    }
+    sm = wave_sum(sm);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sm;
+    __syncthreads();
+    sm = (red[0] + red[1]) + (red[2] + red[3]);
+    const float inv = sm > 0.f ? 1.f / sm : 0.f;
+    // the softmax row (every column; the transcript's columns are rewritten below)
+    const float ls2 = ls * L2E;
+    constexpr int E = 16 / (int)sizeof(T);
+    const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+    const int nv = vec ? V / E : 0;
+    for (int c = threadIdx.x; c < nv; c += 256) {
+        T v[E], o[E];
+        *reinterpret_cast<u32x4*>(v) = *reinterpret_cast<const u32x4*>(x + c * E);
+#pragma unroll
+        for (int e = 0; e < E; ++e) o[e] = from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(to_f32(v[e]), L2E, -ls2)) * gscale);
+        *reinterpret_cast<u32x4*>(g + c * E) = *reinterpret_cast<const u32x4*>(o);
+    }
+    for (int c = nv * E + threadIdx.x; c < V; c += 256)
+        g[c] = from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(to_f32(x[c]), L2E, -ls2)) * gscale);
+    const int* rp = rep + (long)b * Rrow;
+    for (int k0 = 0; k0 <= L; k0 += CTC_ANY_ITEMS) {
+        const int kn = min(CTC_ANY_ITEMS, L + 1 - k0);
+        for (int k = threadIdx.x; k < kn; k += 256) occ[k] = 0ull;
+        __syncthreads();                                           // (also orders the row stores above before the rewrites below)
+        for (int s = threadIdx.x; s < S; s += 256) {
+            const int r = rp[(s & 1) ? (s >> 1) + 1 : 0] - k0;
+            if (r >= 0 && r < kn) {
+                const float w = weight(s);
+                if (w > -INFINITY)
+                    atomicAdd(&occ[r], (unsigned long long)((double)(__builtin_amdgcn_exp2f(w - mx) * inv) * CTC_ANY_FIX));
+            }
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < kn; k += 256) {
+            if (rp[k0 + k] != k0 + k) continue;                    // a repeat: its posteriors went to the first occurrence
+            const int c = ctc_any_col(tg, k0 + k == 0 ? 0 : 2 * (k0 + k) - 1, blank, V);
+            const float o = (float)((double)occ[k] * (1.0 / CTC_ANY_FIX));
+            g[c] = from_f32<T>((__builtin_amdgcn_exp2f(__builtin_fmaf(to_f32(x[c]), L2E, -ls2)) - o) * gscale);
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" size_t s2t_ctc_loss_any_workspace(int T, int B, int Lmax, int V) {
+    (void)V;
+    if (T <= 0 || B <= 0 || Lmax < 0) return 0;
+    return 4 * (2 * (size_t)B * T * CTC_ANY_ROW(Lmax) + (size_t)B * CTC_ANY_REP(Lmax));
+}
+
+extern "C" int s2t_ctc_loss_any(int dtype, const void* logits, const long long* targets, const long long* tgt_len,
+                                const int* in_len, float* lse, void* ws, float* nll, void* grad, float* loss_sum, int T, int B,
+                                int V, int ld, int Lmax, int blank, float grad_scale, int phase, const float* grad_scale_dev,
+                                void* stream) {
+    if (B <= 0 || T <= 0) return S2T_OK;
+    const bool lse_given = (phase & 4) != 0;
+    phase &= 3;
+    if (!logits || !targets || !tgt_len || !in_len || !lse || !ws || !nll || V <= 0 || ld < V || Lmax < 0 || phase > 2) return S2T_EINVAL;
+    if ((phase != 2 && !loss_sum) || (phase != 1 && !grad)) return S2T_EINVAL;
+    if (dtype != S2T_BF16 && dtype != S2T_F32) return S2T_ENOTSUP;
+    const bool fwd = phase != 2, bwd = phase != 1;
+    const long R = CTC_ANY_ROW(Lmax), RR = CTC_ANY_REP(Lmax);
+    float* la = (float*)ws;
+    float* lb = la + (size_t)B * T * R;
+    int* rep = (int*)(lb + (size_t)B * T * R);
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)T * B;
+    const int nt = (int)min(R, 1024l);                          // recursion: threads per (utterance, direction)
+    const dim3 g1((unsigned)((rows + 3) / 4)), g3(T, B);
+    if (fwd) {
+        if (dtype == S2T_BF16) {
+            if (!lse_given) hipLaunchKernelGGL(row_lse_kernel<bf16>, g1, dim3(256), 0, st, (const bf16*)logits, lse, rows, V, ld);
+            hipLaunchKernelGGL(ctc_emit_any_kernel<bf16>, g3, dim3(256), 0, st, (const bf16*)logits, lse, targets, tgt_len, in_len, la, lb, T, B, V, ld, Lmax, R, blank);
+        } else {
+            if (!lse_given) hipLaunchKernelGGL(row_lse_kernel<float>, g1, dim3(256), 0, st, (const float*)logits, lse, rows, V, ld);
+            hipLaunchKernelGGL(ctc_emit_any_kernel<float>, g3, dim3(256), 0, st, (const float*)logits, lse, targets, tgt_len, in_len, la, lb, T, B, V, ld, Lmax, R, blank);
+        }
+        hipLaunchKernelGGL(ctc_rep_any_kernel, dim3(B), dim3(1024), 0, st, targets, tgt_len, rep, Lmax, RR, blank);
+        hipLaunchKernelGGL(ctc_alphabeta_any_kernel, dim3(B, 2), dim3(nt), 0, st, targets, tgt_len, in_len, la, lb, nll, T, Lmax, R, blank);
+        hipLaunchKernelGGL(ctc_loss_sum_kernel, dim3(1), dim3(64), 0, st, nll, B, loss_sum);
+    }
+    if (bwd) {
+        if (dtype == S2T_BF16)
+            hipLaunchKernelGGL(ctc_grad_any_kernel<bf16>, g3, dim3(256), 0, st, (const bf16*)logits, lse, targets, tgt_len, in_len, la, lb, rep, nll, (bf16*)grad, T, B, V, ld, Lmax, R, RR, blank, grad_scale, grad_scale_dev);
+        else
+            hipLaunchKernelGGL(ctc_grad_any_kernel<float>, g3, dim3(256), 0, st, (const float*)logits, lse, targets, tgt_len, in_len, la, lb, rep, nll, (float*)grad, T, B, V, ld, Lmax, R, RR, blank, grad_scale, grad_scale_dev);
+    }
+    S2T_LAUNCH_CHECK();
+    return S2T_OK;
+}

@@ -404,45 +404,62 @@ def ctc_compress_bwd(dout, w, seg, dx, accumulate=False):
 CTC_MAX_TARGET, CTC_MAX_VOCAB = 511, 40704        # S2T_CTC_MAX_TARGET / S2T_CTC_MAX_VOCAB of include/s2t_hip.h
 
 
-def ctc_loss(logits, targets, tgt_len, in_len32, blank, grad_scale=1.0, defer_grad=False, lse=None):
+def ctc_loss(logits, targets, tgt_len, in_len32, blank, grad_scale=1.0, defer_grad=False, lse=None, route="auto"):
     """Returns (loss_sum f32[1], grad like logits, nll).  defer_grad: the forward pass only; the second result is then the workspace
-    tuple for ctc_loss_grad (called from backward with the upstream gradient as a device scalar: no separate scaling pass)."""
+    tuple for ctc_loss_grad (called from backward with the upstream gradient as a device scalar: no separate scaling pass).
+    route "auto": s2t_ctc_loss within its limits (transcripts of at most CTC_MAX_TARGET units, vocabularies of at most
+    CTC_MAX_VOCAB entries), s2t_ctc_loss_any beyond them; "any" runs s2t_ctc_loss_any whatever the shape."""
     T, B, V = logits.shape
     Lmax = targets.shape[1]
-    if Lmax > CTC_MAX_TARGET or V > CTC_MAX_VOCAB:
-        raise L.S2THipError("CTC loss kernels take transcripts of at most %d units and vocabularies of at most %d entries "
-                            "(S2T_CTC_MAX_TARGET / S2T_CTC_MAX_VOCAB, include/s2t_hip.h); this batch has %d / %d: filter the data "
-                            "with --max-target-positions or shorten the transcripts" % (CTC_MAX_TARGET, CTC_MAX_VOCAB, Lmax, V))
+    if route not in ("auto", "any"):
+        raise ValueError("ctc_loss route must be 'auto' or 'any', got %r" % (route,))
+    if route == "auto":
+        route = "fixed" if Lmax <= CTC_MAX_TARGET and V <= CTC_MAX_VOCAB else "any"
     dev = logits.device
-    S = next(r for r in (64, 128, 256, 512, 1024) if 2 * Lmax + 1 <= r)      # S2T_CTC_ROW(Lmax), include/s2t_hip.h
     lse_given = lse is not None                     # row log-sum-exps of THESE logits from ctc_argmax(want_lse=True)
     if lse is None:
         lse = torch.empty((T * B,), dtype=torch.float32, device=dev)
     assert lse.numel() == T * B and lse.dtype == torch.float32
-    la = torch.empty((B * T * S,), dtype=torch.float32, device=dev)
-    lb = torch.empty((B * T * S,), dtype=torch.float32, device=dev)
     nll = torch.empty((B,), dtype=torch.float32, device=dev)
     ld = _row_ld(logits)
     grad = None if defer_grad else torch.empty((T, B, ld), dtype=logits.dtype, device=dev)[..., :V]
     loss = torch.zeros((1,), dtype=torch.float32, device=dev)
-    L.check(_lib().s2t_ctc_loss(L.dt(logits), L.ptr(logits), L.ptr(targets), L.ptr(tgt_len), L.ptr(in_len32), L.ptr(lse),
-                                L.ptr(la), L.ptr(lb), L.ptr(nll), L.ptr(grad), L.ptr(loss), T, B, V, ld, Lmax, blank,
-                                float(grad_scale), (1 if defer_grad else 0) | (4 if lse_given else 0), 0, L.stream()), "s2t_ctc_loss")
+    phase = (1 if defer_grad else 0) | (4 if lse_given else 0)
+    if route == "fixed":
+        S = next(r for r in (64, 128, 256, 512, 1024) if 2 * Lmax + 1 <= r)      # S2T_CTC_ROW(Lmax), include/s2t_hip.h
+        la = torch.empty((B * T * S,), dtype=torch.float32, device=dev)
+        lb = torch.empty((B * T * S,), dtype=torch.float32, device=dev)
+        L.check(_lib().s2t_ctc_loss(L.dt(logits), L.ptr(logits), L.ptr(targets), L.ptr(tgt_len), L.ptr(in_len32), L.ptr(lse),
+                                    L.ptr(la), L.ptr(lb), L.ptr(nll), L.ptr(grad), L.ptr(loss), T, B, V, ld, Lmax, blank,
+                                    float(grad_scale), phase, 0, L.stream()), "s2t_ctc_loss")
+    else:
+        nbytes = _lib().s2t_ctc_loss_any_workspace(T, B, Lmax, V)
+        la = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)      # the whole workspace; lb unused on this route
+        lb = None
+        L.check(_lib().s2t_ctc_loss_any(L.dt(logits), L.ptr(logits), L.ptr(targets), L.ptr(tgt_len), L.ptr(in_len32), L.ptr(lse),
+                                        L.ptr(la), L.ptr(nll), L.ptr(grad), L.ptr(loss), T, B, V, ld, Lmax, blank,
+                                        float(grad_scale), phase, 0, L.stream()), "s2t_ctc_loss_any")
     if defer_grad:
-        return loss, (logits, targets, tgt_len, in_len32, lse, la, lb, nll, blank, float(grad_scale)), nll
+        return loss, (logits, targets, tgt_len, in_len32, lse, la, lb, nll, blank, float(grad_scale), route), nll
     return loss, grad, nll
 
 
 def ctc_loss_grad(ws, upstream):
-    """gradient w.r.t. the logits from the workspaces of ctc_loss(defer_grad=True), times the device scalar `upstream` (f32[1])"""
-    logits, targets, tgt_len, in_len32, lse, la, lb, nll, blank, grad_scale = ws
+    """gradient w.r.t. the logits from the workspaces of ctc_loss(defer_grad=True), times the device scalar `upstream` (f32[1]),
+    on the route that produced them"""
+    logits, targets, tgt_len, in_len32, lse, la, lb, nll, blank, grad_scale, route = ws
     T, B, V = logits.shape
     ld = _row_ld(logits)
     grad = torch.empty((T, B, ld), dtype=logits.dtype, device=logits.device)[..., :V]
     assert upstream.dtype == torch.float32 and upstream.numel() == 1
-    L.check(_lib().s2t_ctc_loss(L.dt(logits), L.ptr(logits), L.ptr(targets), L.ptr(tgt_len), L.ptr(in_len32), L.ptr(lse),
-                                L.ptr(la), L.ptr(lb), L.ptr(nll), L.ptr(grad), 0, T, B, V, ld, targets.shape[1], blank,
-                                grad_scale, 2, L.ptr(upstream), L.stream()), "s2t_ctc_loss")
+    if route == "fixed":
+        L.check(_lib().s2t_ctc_loss(L.dt(logits), L.ptr(logits), L.ptr(targets), L.ptr(tgt_len), L.ptr(in_len32), L.ptr(lse),
+                                    L.ptr(la), L.ptr(lb), L.ptr(nll), L.ptr(grad), 0, T, B, V, ld, targets.shape[1], blank,
+                                    grad_scale, 2, L.ptr(upstream), L.stream()), "s2t_ctc_loss")
+    else:
+        L.check(_lib().s2t_ctc_loss_any(L.dt(logits), L.ptr(logits), L.ptr(targets), L.ptr(tgt_len), L.ptr(in_len32), L.ptr(lse),
+                                        L.ptr(la), L.ptr(nll), L.ptr(grad), 0, T, B, V, ld, targets.shape[1], blank,
+                                        grad_scale, 2, L.ptr(upstream), L.stream()), "s2t_ctc_loss_any")
     return grad
 
 

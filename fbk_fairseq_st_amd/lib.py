@@ -56,6 +56,8 @@ SIGNATURES = {
     "s2t_ctc_compress_fwd": [c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "s2t_ctc_compress_bwd": [c_int, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "s2t_ctc_loss": [c_int, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P],
+    "s2t_ctc_loss_any_workspace": [c_int, c_int, c_int, c_int],     # returns size_t
+    "s2t_ctc_loss_any": [c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P],
     "s2t_lsce": [c_int, P, P, P, P, c_long, c_int, c_int, c_float, c_int, c_float, P],
     "s2t_kd_loss": [c_int, P, P, P, P, P, P, c_long, c_int, c_int, c_int, c_float, c_float, c_int, c_float, P],
     "s2t_embed_fwd": [c_int, P, P, P, P, c_int, c_int, c_int, c_float, c_int, c_int, P],
@@ -180,7 +182,8 @@ def build(verbose=False):
 # never built here): both call the same libs2t_hip.so, neither computes anything.
 FAST_PATH = os.path.join(_HERE, "_s2t_fastcall.so")
 _HOST_SIDE = ("s2t_host_batch_by_size", "s2t_host_ctc_uer")          # CPU work: release the GIL around the call, as ctypes does
-_SIZE_T_RESULT = ("s2t_gemm_relu_mask_bytes", "s2t_layer_ws_bytes", "s2t_layer_bwd_tmp_bytes", "s2t_decode_lds_bytes")
+_SIZE_T_RESULT = ("s2t_gemm_relu_mask_bytes", "s2t_layer_ws_bytes", "s2t_layer_bwd_tmp_bytes", "s2t_decode_lds_bytes",
+                  "s2t_ctc_loss_any_workspace")
 
 
 def signature_hash():

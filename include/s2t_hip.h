@@ -280,9 +280,9 @@ int s2t_ctc_compress_bwd(int dtype, const void* dout, const float* w, const int*
  * grad_scale_dev[0] (the upstream gradient autograd hands to backward).  phase 0: loss and gradient in one call;
  * phase 1: loss only (workspaces kept by the caller); phase 2: the gradient from the workspaces of a phase-1 call;
  * phase | 4: `lse` already holds the row log-sum-exps of these logits (written by s2t_ctc_argmax), skip that pass.
- * Limits (the reference's F.ctc_loss has none): transcripts of at most S2T_CTC_MAX_TARGET units (Lmax, the padded width of
- * `targets`) and vocabularies of at most S2T_CTC_MAX_VOCAB entries; beyond them the call returns -95 (ENOTSUP) and the host side
- * (criterions.py) refuses the batch with the limit in the message. */
+ * Limits of THIS entry point: transcripts of at most S2T_CTC_MAX_TARGET units (Lmax, the padded width of `targets`) and
+ * vocabularies of at most S2T_CTC_MAX_VOCAB entries; beyond them the call returns -95 (ENOTSUP).  s2t_ctc_loss_any below has
+ * no such limits (the reference's F.ctc_loss has none either); the host side (kernels.py ctc_loss) routes larger batches there. */
 #define S2T_CTC_MAX_TARGET 511
 #define S2T_CTC_MAX_VOCAB 40704
 /* row stride of the la / lb workspaces: the 2*Lmax+1 extended-target positions rounded up to 64 x {1, 2, 4, 8, 16} */
@@ -291,6 +291,17 @@ int s2t_ctc_loss(int dtype, const void* logits, const long long* targets, const 
                  float* lse, float* la, float* lb, float* nll, void* grad, float* loss_sum,
                  int T, int B, int V, int ld, int Lmax, int blank, float grad_scale, int phase, const float* grad_scale_dev,
                  void* stream);
+/* The same loss and gradient for any transcript length and any vocabulary size (csrc/ctc.hip: the recursion keeps its state in
+ * the workspace, the gradient pass needs no vocabulary-sized LDS row).  Arguments and `phase` as s2t_ctc_loss; la / lb are
+ * replaced by ONE workspace `ws` of s2t_ctc_loss_any_workspace(T, B, Lmax, V) bytes:
+ *     4 * (2 * B * T * R + B * Q)   with R = 2 * Lmax + 1 and Q = Lmax + 1, each rounded up to a multiple of 64
+ * (alpha and beta rows of R floats per frame, then Q ints per utterance).  Private to the two phases of one loss; a phase-2 call
+ * must pass the same ws, lse, nll and inputs as its phase-1 call.  V is not part of the size (it is taken for future layouts). */
+size_t s2t_ctc_loss_any_workspace(int T, int B, int Lmax, int V);
+int s2t_ctc_loss_any(int dtype, const void* logits, const long long* targets, const long long* tgt_len, const int* in_len,
+                     float* lse, void* ws, float* nll, void* grad, float* loss_sum,
+                     int T, int B, int V, int ld, int Lmax, int blank, float grad_scale, int phase, const float* grad_scale_dev,
+                     void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
