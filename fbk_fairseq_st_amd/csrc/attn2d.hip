@@ -66,18 +66,19 @@ __global__ __launch_bounds__(256) void a2d_stats_kernel(const T* __restrict__ z,
     }
 }
 
-// y = relu(prescale*z*scale + shift) [+ res]
+// y = relu(prescale*z*scale + shift) [+ res]; whole rows of y are written: padding channels C..ld_y-1 get res (zero without res),
+// as the vectorised form's 16-byte stores do
 template <typename T>
 __global__ __launch_bounds__(256) void a2d_bn_act_kernel(const T* __restrict__ z, const float* __restrict__ prescale, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, const T* __restrict__ res, T* __restrict__ y,
                                                          long M, int C, int ld_z, int ld_y) {
-    const long n = M * C;
+    const long n = M * ld_y;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long r = i / C; const int c = (int)(i % C);
-        float v = to_f32(z[r * ld_z + c]) * (prescale ? prescale[c] : 1.f) * scale[c] + shift[c];
-        v = fmaxf(v, 0.f);
-        if (res) v += to_f32(res[r * ld_y + c]);
-        y[r * ld_y + c] = from_f32<T>(v);
+        const long r = i / ld_y; const int c = (int)(i % ld_y);
+        float v = 0.f;
+        if (c < C) v = fmaxf(to_f32(z[r * ld_z + c]) * (prescale ? prescale[c] : 1.f) * scale[c] + shift[c], 0.f);
+        if (res) v += to_f32(res[i]);
+        y[i] = from_f32<T>(v);
     }
 }
 
@@ -646,7 +647,7 @@ __global__ __launch_bounds__(256) void a2d_conv_wgrad_kernel(const T* __restrict
     // partial sums of this workgroup -> ws[blockIdx.x][CO][CI][9]; PS frame subsets add up through LDS first.  (One f32 atomic per
     // weight per workgroup was 4.7 M atomics on 9 K addresses: 200-280 us of same-address contention, measured.)
     __syncthreads();
-    float* red = a2d_lds;                                  // [CO*CI*9] floats (<= 36 KB, fits in the staging area)
+    float* red = a2d_lds;                                  // [CO*CI*9] floats (<= 36 KB; the host sizes the allocation for it)
     for (int rep = 0; rep < PS; ++rep) {
         if (active && ps == rep) {
 #pragma unroll
@@ -755,8 +756,8 @@ extern "C" int s2t_a2d_bn_act(int dtype, const void* z, const float* prescale, c
         return S2T_OK;
     }
     A2D_DISPATCH_T(dtype,
-        hipLaunchKernelGGL(a2d_bn_act_kernel<bf16>, dim3(grid_for(M * C)), dim3(256), 0, st, (const bf16*)z, prescale, scale, shift, (const bf16*)res, (bf16*)y, M, C, ld_z, ld_y),
-        hipLaunchKernelGGL(a2d_bn_act_kernel<float>, dim3(grid_for(M * C)), dim3(256), 0, st, (const float*)z, prescale, scale, shift, (const float*)res, (float*)y, M, C, ld_z, ld_y));
+        hipLaunchKernelGGL(a2d_bn_act_kernel<bf16>, dim3(grid_for(M * ld_y)), dim3(256), 0, st, (const bf16*)z, prescale, scale, shift, (const bf16*)res, (bf16*)y, M, C, ld_z, ld_y),
+        hipLaunchKernelGGL(a2d_bn_act_kernel<float>, dim3(grid_for(M * ld_y)), dim3(256), 0, st, (const float*)z, prescale, scale, shift, (const float*)res, (float*)y, M, C, ld_z, ld_y));
     S2T_LAUNCH_CHECK();
     return S2T_OK;
 }
@@ -861,7 +862,7 @@ extern "C" int s2t_a2d_freq_bwd(int dtype, const void* qkv, const void* dcat, co
 extern "C" int s2t_a2d_conv_wgrad(int dtype, const void* dY, int ld_dy, const void* X, int ld_x, float* dW, float* ws, int CO, int CI,
                                   int B, int T, int F, void* stream) {
     if (B <= 0 || T <= 0) return S2T_OK;
-    if (!dY || !X || !dW || !ws || F <= 0 || ld_dy < CO || ld_x < CI) return S2T_EINVAL;
+    if (!dY || !X || !dW || !ws || F <= 0 || CO <= 0 || CI <= 0 || ld_dy < CO || ld_x < CI) return S2T_EINVAL;
     const int E = dtype == S2T_BF16 ? 8 : 4;
     if ((ld_dy % E) || (ld_x % E) || (((uintptr_t)dY | (uintptr_t)X) & 15)) return S2T_ENOTSUP;
     const int TT = 6;
@@ -871,7 +872,8 @@ extern "C" int s2t_a2d_conv_wgrad(int dtype, const void* dY, int ld_dy, const vo
     // (CO padded to 16, CI) = (16, 64): in_proj with its 12 real output channels; (64, 8): out_proj
 #define A2D_WGRAD(TT_, COp, CIp, co_real)                                                                                              \
     do {                                                                                                                               \
-        const size_t lds = ((size_t)(TT + 2) * (F + 2) * CIp + (size_t)TT * F * COp) * 4;                                              \
+        const size_t stage = ((size_t)(TT + 2) * (F + 2) * CIp + (size_t)TT * F * COp) * 4, red = (size_t)COp * CIp * 9 * 4;       \
+        const size_t lds = stage > red ? stage : red;           /* the reduction reuses the staging area: small F needs more */  \
         if (lds > 150 * 1024) return S2T_ENOTSUP;                                                                                      \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&a2d_conv_wgrad_kernel<TT_, COp, CIp>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((a2d_conv_wgrad_kernel<TT_, COp, CIp>), dim3(grid), dim3(256), lds, st, (const TT_*)dY, ld_dy, (const TT_*)X, ld_x, ws, B, T, F, TT, units); \

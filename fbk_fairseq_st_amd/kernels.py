@@ -751,6 +751,7 @@ def a2d_time_bwd(qkv, cat, dcat, lse, dqkv, B, T, F, p_drop=0.0, seed=0):
     delta = torch.empty_like(lse)
     L.check(_lib().s2t_a2d_time_bwd(L.dt(qkv), L.ptr(qkv), L.ptr(cat), L.ptr(dcat), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), B, T, F,
                                     float(p_drop), int(seed), L.stream()), "s2t_a2d_time_bwd")
+    return delta
 
 
 def a2d_freq_fwd(qkv, cat, B, T, F, p_drop=0.0, seed=0):
