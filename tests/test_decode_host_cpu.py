@@ -3,6 +3,7 @@ records.  The records are produced here by a numpy re-enactment of the reference
 the tokens / scores buffers re-ordered by the chosen parents every step), so the walk over parent links must give back exactly the
 buffers' rows."""
 import numpy as np
+import pytest
 
 from fbk_fairseq_st_amd.decode import _pick_hidden_slice, walk_records
 
@@ -48,6 +49,65 @@ def test_walk_records_rebuilds_the_reordered_buffers():
         assert tok[f, :n].tolist() == et.tolist()
         np.testing.assert_array_equal(pos[f, :n], ep)
         assert score[f] == es and int(org[f]) == int(eo)
+
+
+@pytest.mark.parametrize("seed,B,beam,V,max_len,min_len,unk_pen,temp,eos_scale,lenpen", [
+    (1, 2, 3, 11, 6, 1, 0.0, 1.0, 4.0, 1.0),           # EOS-rich: sentences finalise at different steps, slots get black-listed
+    (2, 3, 2, 9, 5, 3, 0.5, 1.3, 3.0, 0.7),            # min_len, unk penalty, temperature
+    (3, 1, 4, 9, 4, 4, 0.0, 1.0, 1.0, 1.0),            # min_len = max_len: every hypothesis ends at the forced-EOS step; V = 2 beam + 1
+    (4, 2, 1, 13, 7, 1, 0.0, 0.8, 5.0, 1.0),           # beam 1
+])
+def test_restated_bookkeeping_reproduces_the_oracle_search(seed, B, beam, V, max_len, min_len, unk_pen, temp, eos_scale, lenpen):
+    """tests/decode_ref.sent_step (the GPU test's restatement of dec_sent_kernel) driven by oracle/s2t_ref.py's own fp32 log-probs:
+    every row's 2 beam best (value descending, column ascending), then the restated merge / finalisation / next beam; the records
+    walked back by decode.walk_records must give s2t_ref's hypotheses (tokens exact, scores to f32 rounding)."""
+    import math
+    import torch
+    import decode_ref as R
+    from oracle import s2t_ref
+    D, pad, eos, unk = 64, 1, 2, 3
+    cfg = s2t_ref.default_cfg(D=D, heads=1, ffn=64, enc_layers=0, dec_layers=1)
+    W = s2t_ref.make_weights({k: v for k, v in s2t_ref.param_shapes(cfg, 8, V).items() if k.startswith("decoder.")}, seed)
+    W["decoder.output_projection.weight"][eos] *= eos_scale
+    rs = np.random.RandomState(seed)
+    n = [int(v) for v in rs.randint(3, 9, size=B)]
+    eo = [torch.from_numpy(rs.randn(n[b], 1, D).astype(np.float32)) for b in range(B)]
+    N, K2 = B * beam, 2 * beam
+    st = R.new_state(B, beam, max_len, eos)
+    prefix = [[eos] for _ in range(N)]
+    for t in range(max_len + 1):
+        if bool(st["finished"].all()):
+            break
+        cand_val = np.full((N, K2), -np.inf, np.float32)
+        cand_idx = np.tile(np.arange(K2, dtype=np.int32), (N, 1))     # idle slots of the first step: -inf in column order
+        for b in range(B):
+            toks = torch.tensor([prefix[b * beam + j] for j in range(beam)], dtype=torch.long)
+            lp = torch.log_softmax(s2t_ref.decoder_forward(W, cfg, toks, eo[b].expand(n[b], beam, D), None)[:, -1, :] / temp, dim=-1)
+            lp[lp != lp] = -math.inf
+            lp[:, pad] = -math.inf
+            lp[:, unk] -= unk_pen
+            if t >= max_len:
+                keep = lp[:, eos].clone(); lp[:] = -math.inf; lp[:, eos] = keep
+            elif t < min_len:
+                lp[:, eos] = -math.inf
+            for j in range(beam if t > 0 else 1):
+                r = b * beam + j
+                v = (lp[j] + torch.from_numpy(st["cum_hist"][t, r:r + 1])).numpy() if t > 0 else lp[j].numpy()
+                order = np.lexsort((np.arange(V), -v.astype(np.float64)))[:K2]
+                cand_val[r], cand_idx[r] = v[order], order
+        R.sent_step(st, cand_val, cand_idx, beam, V, eos, max_len, False)
+        prefix = [prefix[int(st["par_hist"][t + 1, r])] + [int(st["tok_hist"][t + 1, r])] for r in range(N)]
+    sent, tok, pos, score, _, length = walk_records(st["tok_hist"], st["par_hist"], st["cum_hist"], st["nfin"], st["fin_step"],
+                                                    st["fin_row"], st["fin_score"], beam, pad, eos, True, lenpen)
+    for b in range(B):
+        exp = s2t_ref._beam_search_sentence(W, cfg, eo[b], n[b], beam, max_len, min_len, lenpen, unk_pen, temp, True, eos, unk)
+        mine = [f for f in range(sent.shape[0]) if int(sent[f]) == b]
+        mine = [mine[i] for i in reversed(sorted(range(len(mine)), key=lambda i: float(score[mine[i]])))]
+        assert len(mine) == len(exp) == beam
+        for f, (et, esc, eps, _) in zip(mine, exp):
+            assert tok[f, :int(length[f])].tolist() == et.tolist()
+            assert abs(float(score[f]) - esc) <= 1e-5 * max(1.0, abs(esc))
+            np.testing.assert_allclose(pos[f, :int(length[f])], eps.numpy(), rtol=0, atol=1e-5)
 
 
 def test_hidden_slice_choice():
