@@ -10,6 +10,8 @@ The header promises that the route options change nothing beyond rounding.  Each
 
 A missing or doubled k-tile, a tile written by the wrong workgroup or a dropped ragged row misses these bounds by orders of
 magnitude; rounding stays well inside them.  tests/test_route_options_cpu.py checks that every option key is set somewhere here.
+Attention here is d = 64 with the default scale; tests/test_attention_modes_gpu.py has d = 32, the distance penalty, LSE, the dropout
+mask itself, s2t_attn_probs_avg and the layouts that leave the second-generation kernels.
 """
 import contextlib
 import math
