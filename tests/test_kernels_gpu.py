@@ -440,6 +440,9 @@ def test_ctc_rle_long_runs():
     c = int_ref.ctc_rle_c(pred.numpy(), lens.numpy())
     assert np.array_equal(new_len.cpu().numpy(), c["new_len"])
     assert np.array_equal(seg.cpu().numpy(), c["seg_id"])
+    for b in range(B):
+        nl = int(c["new_len"][b])
+        assert np.array_equal(rs[b, :nl].cpu().numpy(), c["run_start"][b, :nl]) and np.array_equal(rl[b, :nl].cpu().numpy(), c["run_len"][b, :nl])
 
 
 # ------------------------------------------------------------------ losses
