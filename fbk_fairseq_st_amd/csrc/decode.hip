@@ -984,21 +984,58 @@ __global__ __launch_bounds__(NTHREADS) void dec_logits_kernel(LogitArgs a) {
 // log-softmax of row n (same arithmetic and summation order as log_softmax_kernel of loss_embed.hip), the score rules of
 // sequence_generator.py:263-282 (NaN -> -inf; pad -inf; unk penalty; only EOS at max_len; no EOS before min_len), + the cumulative score
 // of the hypothesis (search.py:62-69), then the K2 = 2*beam best (value descending, column ascending on ties).
+// RULES (s2t_decode_step_rules; the plain instantiation compiles none of it): the two rules that follow those in the reference, in its order.
+//   prefix tokens (:270-280, 449-476): at a step t < prefix_len (and < max_len) a row whose sentence has a token there that is not pad keeps
+//   that column only (with its log-probability, unk penalty included), and the min_len rule is skipped for the whole batch (`elif`);
+//   n-gram blocking (:596-650), n >= 2: with g[0 .. t] the row's tokens (<bos> first), every j with g[j .. j+n-2] == g[t-n+2 .. t] bans
+//   column g[j+n-1].  The history is not stored per row: g[p] = tok_hist[p][anc[n][p]] for p < t, g[t] = tok_hist[t][n] -- a two-deep
+//   gather, requested before the logits are waited for, then held in LDS; the bans are a bitmap of V bits in LDS (atomic OR), read by
+//   the rule loop.  A ban may empty a forced row: the candidate search's exact slow way orders rows full of -inf.
 struct RowArgs {
     int beam, N, V, ldv, K2, pad, unk, eos, max_len, min_len, step0_all; float it, unk_penalty;
     const float* logits; const int* steps; const float* cum_hist; const float* init_scores; float* cand_val; int* cand_idx;
 };
+struct RowRuleArgs : RowArgs { int ngram, prefix_len, maxpos; const int* prefix; const int* tok_hist; const int* anc; };
+template <bool RULES> struct RowArgsOf { typedef RowArgs type; };
+template <> struct RowArgsOf<true> { typedef RowRuleArgs type; };
+constexpr int ROW_HIST = 1024;                                     // positions of a history (max_len + 1 <= 1024), and words of the ban bitmap (V <= 32768)
 __device__ __forceinline__ bool cand_after(float v, int i, float lv, int li) { return v < lv || (v == lv && i > li); }
 __device__ __forceinline__ bool cand_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-template <int VPT>
-__global__ __launch_bounds__(NTHREADS) void dec_row_kernel(RowArgs a) {
+template <int VPT, bool RULES>
+__global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RULES>::type a) {
     __shared__ float sh[16];
     __shared__ float wv[4 * 32];
     __shared__ int wi[4 * 32];
+    __shared__ int g_s[RULES ? ROW_HIST : 1];
+    __shared__ unsigned ban_s[RULES ? ROW_HIST : 1];
     const int n = blockIdx.x, s = n / a.beam, tid = threadIdx.x, V = a.V;
     const int t = a.steps[s];
     if (t > a.max_len) return;
     DSTAMP(3, 0);
+    // RULES: the forced token of this step (pad = none) and the row's history, up to four positions per thread.  Positions past t
+    // repeat position t (never stored).  The ancestor rows are requested before the logits and the tokens behind them, so that both
+    // round trips run under the wait for the logits.
+    int ptok = 0, gv[ROW_HIST / NTHREADS];
+    bool in_prefix = false, blocking = false;
+    if constexpr (RULES) {
+        in_prefix = t < a.prefix_len && t < a.max_len;
+        ptok = in_prefix ? a.prefix[(size_t)s * a.prefix_len + t] : a.pad;
+        blocking = a.ngram > 1 && t + 2 - a.ngram >= 0;
+        if (blocking) {
+            int row[ROW_HIST / NTHREADS];
+#pragma unroll
+            for (int k = 0; k < ROW_HIST / NTHREADS; ++k) {
+                const int p = min(tid + k * NTHREADS, t);
+                row[k] = p < t ? a.anc[(size_t)n * a.maxpos + p] : n;
+            }
+#pragma unroll
+            for (int k = 0; k < ROW_HIST / NTHREADS; ++k) {
+                const int p = min(tid + k * NTHREADS, t);
+                gv[k] = a.tok_hist[(size_t)p * a.N + min(max(row[k], 0), a.N - 1)];
+            }
+            for (int i = tid; i < (V + 31) / 32; i += NTHREADS) ban_s[i] = 0u;
+        }
+    }
     const float* x = a.logits + (size_t)n * a.ldv;
     float val[VPT];
     float m = -INFINITY;
@@ -1019,6 +1056,24 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(RowArgs a) {
     z = block_sum(z, sh);
     const float lse = m + logf(z);
     DSTAMP(3, 1);
+    if constexpr (RULES) {
+        if (blocking) {                                            // the same in every thread of the workgroup
+#pragma unroll
+            for (int k = 0; k < ROW_HIST / NTHREADS; ++k) {
+                const int p = tid + k * NTHREADS;
+                if (p <= t) g_s[p] = gv[k];
+            }
+            __syncthreads();
+            const int ng = a.ngram, h0 = t - ng + 2;               // the last n - 1 tokens: g[h0 .. t]
+            for (int j = tid; j <= t + 1 - ng; j += NTHREADS) {
+                bool same = true;
+                for (int i = 0; i < ng - 1 && same; ++i) same = g_s[j + i] == g_s[h0 + i];
+                const int c = g_s[j + ng - 1];
+                if (same && (unsigned)c < (unsigned)V) atomicOr(&ban_s[c >> 5], 1u << (c & 31));
+            }
+            __syncthreads();
+        }
+    }
     const bool live = t > 0 || a.step0_all || (n % a.beam) == 0;          // step 0: every slot holds the same <bos> (search.py:64-66)
     const float base = t > 0 ? a.cum_hist[(size_t)t * a.N + n] : (a.init_scores ? a.init_scores[n] : 0.f);
 #pragma unroll
@@ -1029,7 +1084,11 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(RowArgs a) {
         if (v == a.pad) lp = -INFINITY;
         if (v == a.unk) lp -= a.unk_penalty;
         if (t >= a.max_len) { if (v != a.eos) lp = -INFINITY; }
+        else if (RULES && in_prefix) { if (ptok != a.pad && v != ptok) lp = -INFINITY; }
         else if (t < a.min_len && v == a.eos) lp = -INFINITY;
+        if constexpr (RULES) {
+            if (blocking && v < V && ((ban_s[v >> 5] >> (v & 31)) & 1u)) lp = -INFINITY;
+        }
         val[i] = (live && v < V) ? lp + base : -INFINITY;
     }
     // K2 best of the row.  Threshold first: every lane's largest value; the K2-th largest lane maximum of a wave is a value that at
@@ -1422,8 +1481,9 @@ void launch_ffn(int hs, dim3 grid, size_t lds, hipStream_t st, const FfnArgs& a)
 int g_s2t_opt_decode_stop_after = 0;      // diagnostic (s2t_set_option "decode_stop_after"): > 0 ends a step after that many launches
 namespace {
 #define DEC_STOP_CHECK() do { if (g_s2t_opt_decode_stop_after > 0 && ++launched >= g_s2t_opt_decode_stop_after) { S2T_LAUNCH_CHECK(); return S2T_OK; } } while (0)
+// r: the rules of s2t_decode_step_rules, or NULL (checked by rules_check)
 template <typename T>
-int step_impl(const S2TDecodeDesc* d, hipStream_t st) {
+int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
     int launched = 0;
     const int B = d->B, R = d->beam, N = B * R, D = d->D, H = d->heads, FS = d->ffn_slices, hs = d->ffn / FS, maxpos = d->max_len + 1;
     const LdsNeed need = lds_need(d);
@@ -1488,13 +1548,17 @@ int step_impl(const S2TDecodeDesc* d, hipStream_t st) {
         DEC_STOP_CHECK();
     }
     {
-        RowArgs a; a.beam = R; a.N = N; a.V = d->V; a.ldv = d->ldv; a.K2 = 2 * R; a.pad = d->pad; a.unk = d->unk; a.eos = d->eos;
+        RowRuleArgs a; a.beam = R; a.N = N; a.V = d->V; a.ldv = d->ldv; a.K2 = 2 * R; a.pad = d->pad; a.unk = d->unk; a.eos = d->eos;
         a.max_len = d->max_len; a.min_len = d->min_len; a.step0_all = d->step0_all_slots; a.it = d->inv_temperature; a.unk_penalty = d->unk_penalty;
         a.logits = d->logits; a.steps = d->steps; a.cum_hist = d->cum_hist; a.init_scores = d->init_scores; a.cand_val = d->cand_val;
         a.cand_idx = d->cand_idx;
         // columns per thread: the kernel is bound by its per-column VALU work on a wave that runs alone on its SIMD, so the unrolled loops
         // are sized to the vocabulary (V = 5,000: 20, not 32)
-#define DEC_ROW(VPT_) hipLaunchKernelGGL(dec_row_kernel<VPT_>, dim3(N), dim3(NTHREADS), 0, st, a)
+        const bool rules = r && (r->no_repeat_ngram > 0 || r->prefix_len > 0);
+        a.ngram = rules ? r->no_repeat_ngram : 0; a.prefix_len = rules ? r->prefix_len : 0; a.prefix = rules ? r->prefix : nullptr;
+        a.maxpos = maxpos; a.tok_hist = d->tok_hist; a.anc = d->anc;
+#define DEC_ROW(VPT_) do { if (rules) hipLaunchKernelGGL((dec_row_kernel<VPT_, true>), dim3(N), dim3(NTHREADS), 0, st, a); \
+                           else hipLaunchKernelGGL((dec_row_kernel<VPT_, false>), dim3(N), dim3(NTHREADS), 0, st, static_cast<const RowArgs&>(a)); } while (0)
         const int vpt = (d->V + NTHREADS - 1) / NTHREADS;
         if (vpt <= 8) DEC_ROW(8); else if (vpt <= 12) DEC_ROW(12); else if (vpt <= 16) DEC_ROW(16); else if (vpt <= 20) DEC_ROW(20);
         else if (vpt <= 24) DEC_ROW(24); else if (vpt <= 32) DEC_ROW(32); else if (vpt <= 40) DEC_ROW(40); else if (vpt <= 48) DEC_ROW(48);
@@ -1563,11 +1627,23 @@ extern "C" int s2t_decode_begin(const S2TDecodeDesc* d, int bos, void* stream) {
     return d->dtype == S2T_BF16 ? begin_impl<bf16>(d, bos, (hipStream_t)stream) : begin_impl<float>(d, bos, (hipStream_t)stream);
 }
 
-extern "C" int s2t_decode_step(const S2TDecodeDesc* d, void* stream) {
-    const int rc = decode_check(d);
-    if (rc != S2T_OK) return rc;
-    return d->dtype == S2T_BF16 ? step_impl<bf16>(d, (hipStream_t)stream) : step_impl<float>(d, (hipStream_t)stream);
+// the rules on their own (before `d` is looked at, and before any launch): see include/s2t_hip.h
+static int rules_check(const S2TDecodeRules* r) {
+    if (!r) return S2T_OK;
+    if (r->no_repeat_ngram < 0 || r->prefix_len < 0 || (r->prefix_len > 0 && !r->prefix)) return S2T_EINVAL;
+    if (r->no_repeat_ngram == 1) return S2T_ENOTSUP;
+    return S2T_OK;
 }
+
+extern "C" int s2t_decode_step_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, void* stream) {
+    if (!d) return S2T_EINVAL;
+    int rc = rules_check(r);
+    if (rc != S2T_OK) return rc;
+    rc = decode_check(d);
+    if (rc != S2T_OK) return rc;
+    return d->dtype == S2T_BF16 ? step_impl<bf16>(d, r, (hipStream_t)stream) : step_impl<float>(d, r, (hipStream_t)stream);
+}
+extern "C" int s2t_decode_step(const S2TDecodeDesc* d, void* stream) { return s2t_decode_step_rules(d, nullptr, stream); }
 
 extern "C" int s2t_decode_prepare_enc(int dtype, const void* kv_enc, void* kp_enc, void* vp_enc, int Ts, int Tsp, int B, int D, int heads, void* stream) {
     if (!kv_enc || !kp_enc || !vp_enc || Ts < 1 || Tsp < Ts || Tsp % 128 || B < 1 || heads < 1 || D != heads * DH) return S2T_EINVAL;
@@ -1594,10 +1670,13 @@ extern "C" int s2t_decode_pack_weight(int dtype, const void* W, int ldw, int N, 
     return S2T_OK;
 }
 
-extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec) {
+extern "C" int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
     if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
     *graph_exec = nullptr;
-    const int rc = decode_check(d);
+    if (!d) return S2T_EINVAL;
+    int rc = rules_check(r);
+    if (rc != S2T_OK) return rc;
+    rc = decode_check(d);
     if (rc != S2T_OK) return rc;
     hipStream_t cs = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
@@ -1607,7 +1686,7 @@ extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void
     int out = S2T_OK;
     e = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed);
     if (e == hipSuccess) {
-        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = d->dtype == S2T_BF16 ? step_impl<bf16>(d, cs) : step_impl<float>(d, cs);
+        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = d->dtype == S2T_BF16 ? step_impl<bf16>(d, r, cs) : step_impl<float>(d, r, cs);
         e = hipStreamEndCapture(cs, &g);
     }
     if (e == hipSuccess && out == S2T_OK) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
@@ -1617,6 +1696,9 @@ extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void
     if (e != hipSuccess) return S2T_EHIP(e);
     *graph_exec = ex;
     return S2T_OK;
+}
+extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec) {
+    return s2t_decode_graph_create_rules(d, nullptr, n_steps, graph_exec);
 }
 extern "C" int s2t_decode_graph_launch(void* graph_exec, void* stream) {
     if (!graph_exec) return S2T_EINVAL;

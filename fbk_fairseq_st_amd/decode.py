@@ -7,9 +7,10 @@ and looks at the `finished` flags every few steps.  Nothing of the state is re-o
 an ancestor table, the encoder-side K/V exist once per sentence, and the hypotheses are read back at the end by walking the
 recorded (token, parent, cumulative score) triples.
 
-`SequenceGenerator` (sequence_generator.py) takes this path for one model with the plain or the hierarchical beam search and
-keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for ensembles, prefix tokens, n-gram blocking
-and attention output.
+`SequenceGenerator` (sequence_generator.py) takes this path for one model with the plain or the hierarchical beam search, with
+n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch (`s2t_decode_step_rules`),
+and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for ensembles, attention output, a prefix
+that holds EOS and n-gram size 1.
 """
 import ctypes
 import os
@@ -35,10 +36,12 @@ def _pick_hidden_slice(ffn, B):
 
 
 class BeamDecodeSession:
-    """State + launch sequence of one beam search.  enc_out [Ts, B, D] (one column per SENTENCE), enc_klen int32 [B] or None."""
+    """State + launch sequence of one beam search.  enc_out [Ts, B, D] (one column per SENTENCE), enc_klen int32 [B] or None.
+    no_repeat_ngram_size: 0 (off) or >= 2 (1 is refused: `ok` False); prefix_tokens: integer [B, P], pad = free, WITHOUT EOS (the
+    caller checks: sequence_generator._device_search) -- the session keeps its int32 device copy alive for the recorded graph."""
 
     def __init__(self, engine, pfx, enc_out, enc_klen, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0,
-                 init_scores=None, step0_all_slots=False):
+                 init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None):
         hp = engine.hp
         Ts, B, D = enc_out.shape
         self.engine, self.B, self.beam, self.N, self.max_len = engine, B, beam, B * beam, max_len
@@ -47,7 +50,9 @@ class BeamDecodeSession:
         N, H, Ff, Ld = self.N, hp.heads, hp.ffn, hp.dec_layers
         Tsp = (Ts + 127) // 128 * 128
         hs = _pick_hidden_slice(Ff, B)
-        self.ok = hs > 0
+        ngram = max(int(no_repeat_ngram_size), 0)
+        self.rules, self.rules_addr = None, None                        # S2TDecodeRules when a rule beyond the descriptor's is set
+        self.ok = hs > 0 and ngram != 1
         if not self.ok:
             return
         FS = Ff // hs
@@ -104,6 +109,17 @@ class BeamDecodeSession:
             assert init_scores.numel() == N
             keep.append(init_scores)
             d.init_scores = init_scores.data_ptr()
+        if prefix_tokens is not None and prefix_tokens.numel() == 0:
+            prefix_tokens = None
+        if ngram or prefix_tokens is not None:
+            r = self.rules = L.DecodeRules()
+            r.no_repeat_ngram = ngram
+            if prefix_tokens is not None:
+                assert prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == B
+                self.prefix = prefix_tokens.to(device=dev, dtype=torch.int32).contiguous()
+                keep.append(self.prefix)
+                r.prefix_len, r.prefix = self.prefix.shape[1], self.prefix.data_ptr()
+            self.rules_addr = ctypes.addressof(r)
         W, P = engine.W, engine.P
         ptr = lambda t: (keep.append(t), t.data_ptr())[1]
 
@@ -152,7 +168,9 @@ class BeamDecodeSession:
         L.check(lib.s2t_decode_begin(self.addr, int(bos), st), "s2t_decode_begin")
         exec_ = ctypes.c_void_p(0)
         per = POLL_STEPS if graph else 1                    # steps per launch: one recorded graph holds POLL_STEPS of them
-        if graph:
+        if graph and self.rules_addr:
+            L.check(lib.s2t_decode_graph_create_rules(self.addr, self.rules_addr, per, ctypes.addressof(exec_)), "s2t_decode_graph_create_rules")
+        elif graph:
             L.check(lib.s2t_decode_graph_create(self.addr, per, ctypes.addressof(exec_)), "s2t_decode_graph_create")
         fo, fn = self.ioff["finished"]
         finished = self.ibuf[fo:fo + fn]
@@ -161,6 +179,8 @@ class BeamDecodeSession:
             while steps < self.max_len + 1:
                 if graph:
                     L.check(lib.s2t_decode_graph_launch(exec_.value, st), "s2t_decode_graph_launch")
+                elif self.rules_addr:
+                    L.check(lib.s2t_decode_step_rules(self.addr, self.rules_addr, st), "s2t_decode_step_rules")
                 else:
                     L.check(lib.s2t_decode_step(self.addr, st), "s2t_decode_step")
                 steps += per                                # (the last graph may run past max_len: its kernels return at once there)

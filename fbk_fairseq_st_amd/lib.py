@@ -103,8 +103,10 @@ SIGNATURES = {
     "s2t_decode_pack_weight": [c_int, P, c_int, c_int, c_int, P, P],
     "s2t_decode_begin": [P, c_int, P],
     "s2t_decode_step": [P, P],
+    "s2t_decode_step_rules": [P, P, P],
     "s2t_decode_lds_bytes": [P],                                # returns size_t
     "s2t_decode_graph_create": [P, c_int, P],
+    "s2t_decode_graph_create_rules": [P, P, c_int, P],
     "s2t_decode_graph_launch": [P, P],
     "s2t_decode_graph_destroy": [P],
     "s2t_host_batch_by_size": [P, c_longlong, P, c_longlong, c_longlong, c_int, P, P, P],
@@ -156,6 +158,11 @@ class DecodeDesc(ctypes.Structure):
                                          "x0", "x1", "part0", "part1", "xn", "logits", "steps", "anc", "cand_val", "cand_idx",
                                          "tok_hist", "par_hist", "cum_hist", "blacklist", "nfin", "finished", "fin_step", "fin_row",
                                          "fin_score")])
+
+
+class DecodeRules(ctypes.Structure):
+    """S2TDecodeRules of include/s2t_hip.h"""
+    _fields_ = [("no_repeat_ngram", c_int), ("prefix_len", c_int), ("prefix", c_void_p)]
 
 
 _lib = None

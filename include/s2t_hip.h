@@ -418,7 +418,11 @@ int s2t_scale_by_device_scalar(int dtype, void* x, size_t n, const float* scalar
  * the encoder-side K/V exist once per sentence.  The step index lives in device memory (steps[s]), so one recorded sequence (a hipGraph
  * captured around s2t_decode_step) serves every step.  Nothing synchronises; the host polls `finished` when it chooses to.
  * Limits (S2T_ENOTSUP otherwise): head size 64, D = 256, 512 or 1024, beam <= 16, B * beam <= 128, ffn / ffn_slices = 64, 128 or 256,
- * max_len + 1 <= 1024 positions, Tsp a multiple of 128, and the LDS plan of every launch within 152 KiB (s2t_decode_lds_bytes). */
+ * max_len + 1 <= 1024 positions, Tsp a multiple of 128, and the LDS plan of every launch within 152 KiB (s2t_decode_lds_bytes).
+ * The *_rules calls add, in the per-row launch and in the reference's order after the rules above, prefix tokens
+ * (sequence_generator.py:270-280,449-476) and n-gram blocking (:596-650); their limits: n-gram size 0 (off) or >= 2 -- with 1 the reference
+ * bans EOS through the <bos> column and the search never finalises (S2T_ENOTSUP); a prefix without EOS -- the reference then copies slot 0
+ * over the sentence's other slots, which this path does not do (the CALLER checks: the tokens are device memory).  One model only. */
 typedef struct S2TDecodeLayer {
     const void *ln1_g, *ln1_b;       /* f32 [D]: self_attn_layer_norm */
     /* every w_* below is the nn.Linear weight in FRAGMENT-MAJOR order (s2t_decode_pack_weight): [rows / 16][K / ks][64 lanes][16 bytes] */
@@ -471,6 +475,16 @@ int s2t_decode_prepare_enc(int dtype, const void* kv, void* kv_enc, void* vt_enc
 int s2t_decode_begin(const S2TDecodeDesc* d, int bos, void* stream);
 /* the launches of one step (see above).  `d` and d->layer are HOST memory read during the call only. */
 int s2t_decode_step(const S2TDecodeDesc* d, void* stream);
+/* Score rules beyond S2TDecodeDesc's, for the calls below.  prefix: DEVICE i32 [B][prefix_len], the forced token of sentence s at step t
+ * or `pad` for none; it must stay where it is while a graph recorded with it is replayed.  At a step t < min(prefix_len, max_len) a row of
+ * a sentence with a forced token keeps that column only (its log-probability after the unk penalty), and the min_len rule is skipped for
+ * EVERY sentence (the reference's `elif`).  no_repeat_ngram = n >= 2: a hypothesis may not produce a token that completes an n-gram it
+ * already contains; applied after the prefix rule (a ban may leave a forced row without any candidate). */
+typedef struct S2TDecodeRules { int no_repeat_ngram, prefix_len; const int* prefix; } S2TDecodeRules;
+/* s2t_decode_step with rules.  r == NULL, or no_repeat_ngram == 0 and prefix_len == 0: exactly s2t_decode_step (which is this call with
+ * NULL).  Checked before any launch: d == NULL, no_repeat_ngram < 0, prefix_len < 0, prefix_len > 0 with prefix == NULL -> S2T_EINVAL;
+ * no_repeat_ngram == 1 -> S2T_ENOTSUP; then `d` as s2t_decode_step checks it.  `r` is HOST memory read during the call only. */
+int s2t_decode_step_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, void* stream);
 /* dynamic LDS bytes the S / C / F launches of `d` need (0 when `d` is outside the limits): the caller may compare with 160 KiB */
 size_t s2t_decode_lds_bytes(const S2TDecodeDesc* d);
 /* n_steps (1..64) consecutive steps recorded as ONE hipGraph: `create` captures n_steps x s2t_decode_step(d) on a private stream (nothing
@@ -479,6 +493,8 @@ size_t s2t_decode_lds_bytes(const S2TDecodeDesc* d);
  * harmless; `d`'s device buffers must stay where they are), `destroy` frees it after the caller has synchronised with the last replay.
  * *graph_exec is HOST. */
 int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec);
+/* the same recording of n_steps x s2t_decode_step_rules(d, r); arguments checked as there (and graph_exec, n_steps first: S2T_EINVAL) */
+int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, int n_steps, void** graph_exec);
 int s2t_decode_graph_launch(void* graph_exec, void* stream);
 int s2t_decode_graph_destroy(void* graph_exec);
 
