@@ -13,6 +13,8 @@
 //
 // Backward = 3 kernels: delta (rowsum(dO*O)), dK/dV (one workgroup per 64 keys, loops over query
 // tiles) and dQ (one workgroup per 64 queries, loops over key tiles): no atomics, deterministic.
+// bf16, d = 64: the second generation (attn_fwd2 / attn_bwd_dq2 / attn_bwd_dkv2, two backward kernels) for long query blocks, and
+// the short-query pair (attn_fwd_sq / attn_bwd_sq, one backward kernel) for Tq <= 64 -- routing: sq_shape, s2t_attn_fwd, bwd_launch.
 #include "common.hpp"
 #include "prof.hpp"
 #include <cstdlib>
@@ -99,8 +101,9 @@ __device__ __forceinline__ void put_tile(char* lds, const f32x4 (&acc)[4], int q
 // transposed variant: acc rows become LDS columns ([16 cols... used when the wave owns 16 "rows"
 // of the TRANSPOSED product: acc[j][r] = X^T[own 4q+r][other 16j+r16] is stored as is (same as put_tile).
 
-// short query blocks over long key ranges (the decoder's encoder-attention: Tq = 40, Tk = 368) also take the second-generation
-// kernels: a workgroup is mostly padding rows there, but each key tile costs a fraction of what the first-generation kernels spend
+// query blocks of 65 .. 127 rows over long key ranges also take the second-generation kernels: a workgroup has padding rows there, but
+// each key tile costs a fraction of what the first-generation kernels spend.  Up to 64 rows (the decoder's encoder-attention: Tq = 40,
+// Tk = 368) go to the short-query kernels below (sq_shape), which have no padding beyond a multiple of 16 rows.
 #define S2T_ATTN_V2_MIN_TQ g_s2t_opt_attn_v2_min_tq      /* s2t_set_option("attn_v2_min_tq") */
 
 struct AttnArgs {
@@ -1166,6 +1169,409 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
     ASTAMP(7, 3)
 }
 
+// ------------------------------------------------------------------------------------ short queries (Tq <= 64), bf16 d = 64
+// The decoder's two attention blocks (encoder-attention: Tq = 40 over ~370 keys; causal self-attention: 40 x 40) have so few
+// queries that ONE workgroup owns all of them for a (batch, head): grid = B H, no workgroup pads its score tiles to 128 query
+// rows, and the backward is a single pass -- S, P, dP, dS and the dropout hash are made once per (query, key), dK / dV of a key
+// tile are complete when its iteration ends and leave with plain stores, dQ stays in registers over the key loop, Delta is made in
+// the prologue (no attn_delta launch, no second kernel).  Staging (LDS-DMA, source-side swizzle), operand orientation and the
+// dropout arithmetic are the second generation's; the mask is the same per-(query, key) hash as in every other kernel.
+//
+// Forward: wave w owns query rows 16 w .. 16 w + 15 (attn_fwd2_kernel with one query block per wave instead of two); a wave whose
+// rows all lie past Tq computes nothing and only helps with the staging.  No score row past the next multiple of 16 above Tq.
+__global__ __launch_bounds__(256, 2) void attn_fwd_sq_kernel(AttnArgs p) {
+    constexpr int DH = 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 stages x (K 8 KiB | V 8 KiB), 512 B of score offsets, Q 8 KiB
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r16 = lane & 15, q = lane >> 4;
+    const int head = blockIdx.x, b = head / p.H, h = head % p.H, qw = wave * 16;
+    const bool active = qw < p.Tq;
+    const int klen = p.klen ? min(p.klen[b], p.Tk) : p.Tk;
+    const bf16* Qg = reinterpret_cast<const bf16*>(p.Q) + (long)b * p.q_sb + (long)h * DH;
+    const bf16* Kg = reinterpret_cast<const bf16*>(p.K) + (long)b * p.k_sb + (long)h * DH;
+    const bf16* Vg = reinterpret_cast<const bf16*>(p.V) + (long)b * p.v_sb + (long)h * DH;
+
+    f32x4 o[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) o[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+    int kv_end = klen;
+    if (p.causal) kv_end = min(kv_end, p.Tq);                       // key <= query < Tq
+    const int ntile = kv_end > 0 ? (kv_end + 63) / 64 : 0;
+
+    // K rows are read back as b128 rows (chunk swizzle row & 7), V by transposing reads (row & 6): attn_fwd2_kernel's staging
+    const uint32_t kst2 = (uint32_t)p.k_st * 2u, vst2 = (uint32_t)p.v_st * 2u;
+    auto stage = [&](int kv0, char* st) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int r8 = 8 * (wave + 4 * i), row = r8 + (lane >> 3), pos = lane & 7;
+            const uint32_t r = (uint32_t)min(kv0 + row, p.Tk - 1);
+            char* dst = st + r8 * 128;
+            const char* ka = reinterpret_cast<const char*>(Kg) + (__umul24(r, kst2) + (uint32_t)((pos ^ (row & 7)) << 4));
+            const char* va = reinterpret_cast<const char*>(Vg) + (__umul24(r, vst2) + (uint32_t)((pos ^ (row & 6)) << 4));
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)ka, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)va, (__attribute__((address_space(3))) void*)(dst + 8192), 16, 0, 0);
+        }
+    };
+    const uint32_t drop_th16 = (uint32_t)fminf(p.p_drop * 4294967296.f, 4294967295.f) >> 16;
+    const uint32_t drop_thm1x2 = (drop_th16 - 1u) * 0x00010001u;
+    const bool has_drop = drop_th16 > 0;               // a rate below 2^-16 keeps every element, as in every other kernel
+    const float drop_inv = 1.f / (1.f - p.p_drop);
+    const uint32_t drop_ks = drop_seed_key(p.seed), drop_hwm = drop_high_mix(p.seed, 0);   // < 2^34 elements (launcher): quad index in one word
+    const uint32_t tkq = (uint32_t)((p.Tk + 3) >> 2);
+    const float sc2 = p.scale * 1.44269504088896f;
+
+    // score offsets of the last key tile of a non-causal call (0 below klen, -inf past it) next to a row of zeros: attn_fwd2_kernel
+    float* sInit = reinterpret_cast<float*>(smem + 32768);              // [2][64]
+    if (threadIdx.x < 128) {
+        const int i = threadIdx.x & 63;
+        sInit[threadIdx.x] = (threadIdx.x < 64 || (ntile - 1) * 64 + i < klen) ? 0.f : -INFINITY;
+    }
+    if (ntile > 0) stage(0, smem);
+    char* sQ = smem + 32768 + 512;                     // the 64 query rows; rows past Tq repeat the last query (finite, never stored)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r8 = 8 * (wave + 4 * i), row = r8 + (lane >> 3), pos = lane & 7;
+        const long r = min(row, p.Tq - 1);
+        __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)(Qg + r * p.q_st + ((pos ^ (row & 7)) << 3)),
+                                         (__attribute__((address_space(3))) void*)(sQ + r8 * 128), 16, 0, 0);
+    }
+    S2T_WAIT_VM0();
+    __syncthreads();
+    const int qrow = qw + r16;
+    const uint32_t qrow_quads = (uint32_t)((b * p.H + h) * p.Tq + qrow) * tkq;
+    for (int t = 0; t < ntile; ++t) {
+        const int kv0 = t * 64;
+        const char* sK = smem + (t & 1) * 16384;
+        const char* sV = sK + 8192;
+        if (t + 1 < ntile) stage(kv0 + 64, smem + ((t + 1) & 1) * 16384);   // its readers of two tiles ago passed the last barrier
+        if (active) {
+            // ---- S^T = K Q^T      acc[r] = S[query r16][key 16 j + 4 q + r]
+            f32x4 s[4];
+            const float* sInit0 = sInit + ((!p.causal && t == ntile - 1) ? 64 : 0) + 4 * q;
+            u32x4 qf[2];
+#pragma unroll
+            for (int g = 0; g < 2; ++g) qf[g] = row_frag128(sQ, qw + r16, 4 * g + q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s[j] = *reinterpret_cast<const f32x4*>(sInit0 + 16 * j);
+#pragma unroll
+                for (int g = 0; g < 2; ++g) s[j] = mma16<bf16>(row_frag128(sK, 16 * j + r16, 4 * g + q), qf[g], s[j]);
+            }
+            // ---- online softmax, per lane = per query, base-2 domain.  MASK: the causal triangle and klen per element (the tail of a
+            // non-causal call rides on the score offsets); the 1/(1-p) of the dropout is applied once, with the 1/l normalisation
+            u32x4 pf[2];                               // [32-key block]
+            auto softmax_tile = [&](auto mask_tag, auto drop_tag) {
+                constexpr bool MASK = decltype(mask_tag)::value, DROP = decltype(drop_tag)::value;
+                float mx = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (MASK) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int key = kv0 + 16 * j + 4 * q + r;
+                            s[j][r] = (key < klen && key <= qrow) ? s[j][r] : -INFINITY;
+                        }
+                    }
+                    mx = fmaxf(fmaxf(mx, s[j][0]), s[j][1]);
+                    mx = fmaxf(fmaxf(mx, s[j][2]), s[j][3]);
+                }
+                mx = max_over_rows(mx);
+                const float mn = fmaxf(m, mx * sc2);
+                const float mu = (mn == -INFINITY) ? 0.f : mn;
+                const float alpha = __builtin_amdgcn_exp2f(m - mu);        // m = -inf -> 0
+                m = mn;
+                f32x2_t rs2 = {0.f, 0.f};
+                const uint32_t qlo = qrow_quads + (uint32_t)((kv0 + 4 * q) >> 2);   // quad of keys 4q .. 4q+3 of 16-key tile j: qlo + 4 j
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float pv[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][r], sc2, -mu));
+                    rs2 += (f32x2_t){pv[0], pv[1]};
+                    rs2 += (f32x2_t){pv[2], pv[3]};
+                    uint32_t p01 = pack_bf16(pv[0], pv[1]), p23 = pack_bf16(pv[2], pv[3]);
+                    if constexpr (DROP) {
+                        const u32x2 hq = drop_hash4_lo(drop_ks, drop_hwm, qlo + 4u * j);
+                        p01 = drop_pair(p01, hq[1], drop_thm1x2); p23 = drop_pair(p23, hq[0], drop_thm1x2);
+                    }
+                    pf[j >> 1][2 * (j & 1)] = p01;
+                    pf[j >> 1][2 * (j & 1) + 1] = p23;
+                }
+                l = l * alpha + (rs2[0] + rs2[1]);
+#pragma unroll
+                for (int n = 0; n < 4; ++n) o[n] *= alpha;
+            };
+            if (p.causal) { if (has_drop) softmax_tile(std::true_type{}, std::true_type{}); else softmax_tile(std::true_type{}, std::false_type{}); }
+            else if (has_drop) softmax_tile(std::false_type{}, std::true_type{});
+            else softmax_tile(std::false_type{}, std::false_type{});
+            // ---- O^T += V^T P^T
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    u32x4 vf;
+#pragma unroll
+                    for (int hh = 0; hh < 2; ++hh) {
+                        const int row = 32 * kb + 16 * hh + 4 * q + (r16 >> 2);
+                        const int ch = 2 * n + ((r16 & 3) >> 1);
+                        const char* a = sV + row * 128 + ((ch ^ (row & 6)) << 4) + ((r16 & 1) << 3);
+                        const s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)a);
+                        const u32x2 w = __builtin_bit_cast(u32x2, v);
+                        vf[2 * hh] = w[0]; vf[2 * hh + 1] = w[1];
+                    }
+                    o[n] = mma16<bf16>(vf, pf[kb], o[n]);
+                }
+        }
+        S2T_WAIT_VM0();                                   // tile t + 1 has landed (this wave's share; the barrier covers the rest)
+        __syncthreads();
+    }
+    float lt = l;
+    lt += __shfl_xor(lt, 16); lt += __shfl_xor(lt, 32);
+    if (qrow >= p.Tq) return;
+    bf16* Og = reinterpret_cast<bf16*>(p.O) + (long)b * p.o_sb + (long)h * DH;
+    const float inv = lt > 0.f ? drop_inv / lt : 0.f;                     // 1/(1-p) whenever p_drop > 0, the backward's predicate (dv_scale)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        u32x2 w;
+        w[0] = pack_bf16(o[n][0] * inv, o[n][1] * inv);
+        w[1] = pack_bf16(o[n][2] * inv, o[n][3] * inv);
+        *reinterpret_cast<u32x2*>(Og + (long)qrow * p.o_st + 16 * n + 4 * q) = w;
+    }
+    if (q == 0 && p.LSE) p.LSE[((long)b * p.H + h) * p.Tq + qrow] = m * 0.693147180559945f + logf(lt);
+}
+
+// Backward, one pass.  Wave w owns keys 16 w .. 16 w + 15 of every 64-key tile and walks all query blocks of 16 against them:
+//   S = Q K^T, dP = dO V^T               acc[r] = X[query 16 i + 4 q + r][key r16]   (A = Q / dO rows from LDS, B = own K / V rows)
+//   dV^T = dO^T (D*P), dK^T = Q^T dS     acc[r] = Y^T[d 16 n + 4 q + r][key r16]      (P / dS straight from the accumulators of two
+//                                        query blocks = one 32-long contraction; an odd last block is paired with zeros, not scores)
+//   dQ += dS K                           acc[r] = dQ[query 16 i + 4 q + r][d 16 n + r16]: the contraction runs over the wave's 16 keys, the
+//                                        index its dS accumulators hold as LANES, so dS (bf16, the MFMA operand it is anyway) makes one
+//                                        trip through a per-wave LDS tile [16 keys][64 queries] and comes back by a transposing read.
+// dK / dV of the tile leave at the end of its iteration (rows from klen to Tk as exact zeros, like the other kernels); the four
+// waves' dQ partials are added once after the loop, through LDS, in wave order: deterministic.
+#define S2T_SQ_TPITCH 136                               /* bytes per key row of the dS tile: 64 queries + 8 bytes against bank conflicts */
+#define S2T_SQ_BWD_LDS (16384 + 512 + 32768 + 4 * 16 * S2T_SQ_TPITCH)
+__global__ __launch_bounds__(256, 2) void attn_bwd_sq_kernel(AttnArgs p) {
+    constexpr int DH = 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];     // Q 8 KiB | dO 8 KiB | LSE, Delta | 2 stages x (K 8 KiB | V 8 KiB) | dS tiles
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r16 = lane & 15, q = lane >> 4;
+    const int head = blockIdx.x, b = head / p.H, h = head % p.H;
+    const int klen = p.klen ? min(p.klen[b], p.Tk) : p.Tk;
+    const bf16* Qg = reinterpret_cast<const bf16*>(p.Q) + (long)b * p.q_sb + (long)h * DH;
+    const bf16* Kg = reinterpret_cast<const bf16*>(p.K) + (long)b * p.k_sb + (long)h * DH;
+    const bf16* Vg = reinterpret_cast<const bf16*>(p.V) + (long)b * p.v_sb + (long)h * DH;
+    const bf16* dOg = reinterpret_cast<const bf16*>(p.dO) + (long)b * p.do_sb + (long)h * DH;
+    const bf16* Og = reinterpret_cast<const bf16*>(p.O) + (long)b * p.o_sb + (long)h * DH;
+    bf16* dKg = reinterpret_cast<bf16*>(p.dK) + (long)b * p.dk_sb + (long)h * DH;
+    bf16* dVg = reinterpret_cast<bf16*>(p.dV) + (long)b * p.dv_sb + (long)h * DH;
+    const float* lse = p.LSE + ((long)b * p.H + h) * p.Tq;
+    float* dlt = const_cast<float*>(p.Delta) + ((long)b * p.H + h) * p.Tq;
+    const char* sQ = smem;
+    const char* sDO = smem + 8192;
+    float* sStat = reinterpret_cast<float*>(smem + 16384);          // [2][64]: LSE * log2 e, Delta
+    char* sKV = smem + 16384 + 512;
+    char* sT = sKV + 32768 + wave * (16 * S2T_SQ_TPITCH);
+
+    int kv_end = klen;
+    if (p.causal) kv_end = min(kv_end, p.Tq);
+    const int ntile = kv_end > 0 ? (kv_end + 63) / 64 : 0;
+    const int nq = (p.Tq + 15) >> 4;                                 // query blocks of 16: 1 .. 4
+    if (ntile > 0) stage2_dma(Kg, p.k_st, Vg, p.v_st, 0, p.Tk, sKV, wave, lane);
+    stage2_dma(Qg, p.q_st, dOg, p.do_st, 0, p.Tq, smem, wave, lane);  // rows past Tq repeat the last query (finite)
+    {   // Delta = rowsum(dO * O): four threads per query row, 16 features each
+        const int row = threadIdx.x >> 2, seg = threadIdx.x & 3;
+        const long rc = min(row, p.Tq - 1);
+        u32x4 of[2], df[2];
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            of[g] = *reinterpret_cast<const u32x4*>(Og + rc * p.o_st + 16 * seg + 8 * g);
+            df[g] = *reinterpret_cast<const u32x4*>(dOg + rc * p.do_st + 16 * seg + 8 * g);
+        }
+        const float L = lse[rc];
+        float part = 0.f;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const bf16* oe = reinterpret_cast<const bf16*>(&of[g]);
+            const bf16* de = reinterpret_cast<const bf16*>(&df[g]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) part += (float)oe[e] * (float)de[e];
+        }
+        part += __shfl_xor(part, 1); part += __shfl_xor(part, 2);
+        if (seg == 0) {
+            // rows past Tq: LSE = +inf, so their probabilities -- and with them dS -- are exact zeros without a mask per element
+            const bool in = row < p.Tq;
+            sStat[row] = in ? L * 1.44269504088896f : INFINITY;
+            sStat[64 + row] = in ? part : 0.f;
+            if (in) dlt[row] = part;                                 // the API exposes Delta
+        }
+    }
+    f32x4 dq[4][4];                                                  // [query block][d block]
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) dq[i][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const uint32_t drop_th16 = (uint32_t)fminf(p.p_drop * 4294967296.f, 4294967295.f) >> 16;
+    const float drop_inv = 1.f / (1.f - p.p_drop);
+    const uint32_t drop_ks = drop_seed_key(p.seed), drop_hwm = drop_high_mix(p.seed, 0);   // < 2^34 elements (launcher): quad index in one word
+    const uint32_t tkq = (uint32_t)((p.Tk + 3) >> 2);
+    const uint32_t drop_thm1x2 = (drop_th16 - 1u) * 0x00010001u;
+    const uint32_t own_bit = ((r16 & 1) ? 0x00010000u : 1u) << ((r16 >> 1) & 1);            // key r16 & 3 of a quad: bits 0, 16, 1, 17
+    const float sc2 = p.scale * 1.44269504088896f;
+    const float dv_scale = p.p_drop > 0.f ? drop_inv : 1.f;
+    S2T_WAIT_VM0();
+    __syncthreads();
+    for (int t = 0; t < ntile; ++t) {
+        const int kv0 = t * 64;
+        const char* sK = sKV + (t & 1) * 16384;
+        const char* sV = sK + 8192;
+        if (t + 1 < ntile) stage2_dma(Kg, p.k_st, Vg, p.v_st, kv0 + 64, p.Tk, sKV + ((t + 1) & 1) * 16384, wave, lane);
+        const int key = kv0 + 16 * wave + r16;                       // the lane's own key
+        f32x4 dkT[4], dvT[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) { dkT[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; dvT[n] = dkT[n]; }
+        // MASK: keys past klen (their tile rows hold whatever lies there: it must be FINITE, as for attn_bwd_dq2_kernel -- their e is an
+        // exact 0, but dP is formed from those rows and 0 x inf would reach dQ) and the causal triangle, per element; DROP: dropout on.
+        // dS carries neither the softmax scale nor, like P, the dropout's 1/(1-p): dK, dQ and dV are scaled once, at their stores.
+        auto tile = [&](auto mask_tag, auto drop_tag) {
+            constexpr bool MASK = decltype(mask_tag)::value, DROP = decltype(drop_tag)::value;
+            u32x4 kfr[2], vfr[2];
+#pragma unroll
+            for (int g = 0; g < 2; ++g) { kfr[g] = row_frag128(sK, 16 * wave + r16, 4 * g + q); vfr[g] = row_frag128(sV, 16 * wave + r16, 4 * g + q); }
+#pragma unroll
+            for (int ib = 0; ib < 2; ++ib) {
+                if (2 * ib >= nq) break;
+                u32x4 pf = {0u, 0u, 0u, 0u}, sf = {0u, 0u, 0u, 0u};   // D*P and dS of 32 queries as B operands
+#pragma unroll
+                for (int ii = 0; ii < 2; ++ii) {
+                    const int i = 2 * ib + ii;
+                    if (i >= nq) break;
+                    u32x4 qa[2], da[2];
+#pragma unroll
+                    for (int g = 0; g < 2; ++g) { qa[g] = row_frag128(sQ, 16 * i + r16, 4 * g + q); da[g] = row_frag128(sDO, 16 * i + r16, 4 * g + q); }
+                    const f32x4 L = *reinterpret_cast<const f32x4*>(sStat + 16 * i + 4 * q);
+                    const f32x4 Dl = *reinterpret_cast<const f32x4*>(sStat + 64 + 16 * i + 4 * q);
+                    f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int g = 0; g < 2; ++g) { st = mma16<bf16>(qa[g], kfr[g], st); dp = mma16<bf16>(da[g], vfr[g], dp); }
+                    // dropout: this lane hashes the quad (query 16 i + 4 q + (r16 & 3), keys 4 (r16 >> 2) ..+3 of the wave's 16) and turns its
+                    // four fields into keep bits (0, 16, 1, 17); the element (query 4 q + r, own key) then costs one DPP quad broadcast
+                    // fused into an AND with the own key's bit: attn_bwd_dkv2_kernel's scheme
+                    uint32_t nib = 0u;
+                    if constexpr (DROP) {
+                        const uint32_t qrow_quads = (uint32_t)((b * p.H + h) * p.Tq + 16 * i + 4 * q + (r16 & 3)) * tkq;
+                        const u32x2 hq = drop_hash4_lo(drop_ks, drop_hwm, qrow_quads + ((uint32_t)key >> 2));
+                        uint32_t dy, dx, ky, kx;
+                        asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dy) : "v"(hq[1]), "v"(drop_thm1x2));
+                        asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dx) : "v"(hq[0]), "v"(drop_thm1x2));
+                        asm("v_pk_min_u16 %0, %1, %2" : "=v"(ky) : "v"(dy), "v"(0x00010001u));
+                        asm("v_pk_min_u16 %0, %1, %2" : "=v"(kx) : "v"(dx), "v"(0x00010001u));
+                        nib = drop_th16 > 0 ? (ky | (kx << 1)) : 0x00030003u;    // a rate below 2^-16 keeps every element
+                    }
+                    float pv[4], ds[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], sc2, -L[r]));
+                        if constexpr (MASK) e = (key < klen && (!p.causal || key <= 16 * i + 4 * q + r)) ? e : 0.f;
+                        if constexpr (DROP) {
+                            const bool keep = (quad_bcast(nib, r) & own_bit) != 0u;
+                            pv[r] = keep ? e : 0.f;
+                            ds[r] = e * __builtin_fmaf(keep ? dp[r] : 0.f, drop_inv, -Dl[r]);
+                        } else {
+                            pv[r] = e;
+                            ds[r] = e * (dp[r] - Dl[r]);
+                        }
+                    }
+                    pf[2 * ii] = pack_bf16(pv[0], pv[1]); pf[2 * ii + 1] = pack_bf16(pv[2], pv[3]);
+                    sf[2 * ii] = pack_bf16(ds[0], ds[1]); sf[2 * ii + 1] = pack_bf16(ds[2], ds[3]);
+                    // dS^T[own key][queries 16 i + 4 q ..+3] for the dQ product below
+                    *reinterpret_cast<u32x2*>(sT + r16 * S2T_SQ_TPITCH + (16 * i + 4 * q) * 2) = (u32x2){sf[2 * ii], sf[2 * ii + 1]};
+                }
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const u32x4 dot = tr_frag128(sDO, ib, n, r16, q), qtf = tr_frag128(sQ, ib, n, r16, q);
+                    dvT[n] = mma16<bf16>(dot, pf, dvT[n]);
+                    dkT[n] = mma16<bf16>(qtf, sf, dkT[n]);
+                }
+            }
+            // ---- dQ += dS K over the wave's 16 keys (16-long contraction: v_mfma_f32_16x16x16_bf16)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's own dS tile is written (only this wave reads it back)
+            __builtin_amdgcn_wave_barrier();
+            s16x4_t kt[4];                                          // B: K[own keys 4 q ..+3][d 16 n + r16]
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int row = 16 * wave + 4 * q + (r16 >> 2), ch = 2 * n + ((r16 & 3) >> 1);
+                kt[n] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(sK + row * 128 + ((ch ^ (row & 7)) << 4) + ((r16 & 1) << 3)));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i >= nq) break;
+                // A: dS[query 16 i + r16][own keys 4 q ..+3]
+                const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                    (__attribute__((address_space(3))) s16x4_t*)(sT + (4 * q + (r16 >> 2)) * S2T_SQ_TPITCH + (16 * i + 4 * (r16 & 3)) * 2));
+#pragma unroll
+                for (int n = 0; n < 4; ++n) dq[i][n] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, kt[n], dq[i][n], 0, 0, 0);
+            }
+            asm volatile("" ::: "memory");                           // the next tile's dS stores stay behind these reads
+        };
+        if (kv0 + 16 * wave < kv_end) {                              // else: all 16 keys are padding or lie above the diagonal -> zeros
+            const bool mask = p.causal || kv0 + 64 > klen;
+            if (p.p_drop > 0.f) { if (mask) tile(std::true_type{}, std::true_type{}); else tile(std::false_type{}, std::true_type{}); }
+            else if (mask) tile(std::true_type{}, std::false_type{});
+            else tile(std::false_type{}, std::false_type{});
+        }
+        S2T_WAIT_VM0();                                   // tile t + 1 has landed (this wave's share; the barrier covers the rest)
+        __syncthreads();
+        // the tile's dK / dV leave AFTER that wait, so it never waits for stores: they drain under the next tile's arithmetic
+        if (key < p.Tk) {
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                dkT[n] *= p.scale; dvT[n] *= dv_scale;
+                u32x2 w;
+                w[0] = pack_bf16(dkT[n][0], dkT[n][1]); w[1] = pack_bf16(dkT[n][2], dkT[n][3]);
+                *reinterpret_cast<u32x2*>(dKg + (long)key * p.dk_st + 16 * n + 4 * q) = w;
+                w[0] = pack_bf16(dvT[n][0], dvT[n][1]); w[1] = pack_bf16(dvT[n][2], dvT[n][3]);
+                *reinterpret_cast<u32x2*>(dVg + (long)key * p.dv_st + 16 * n + 4 * q) = w;
+            }
+        }
+    }
+    // keys of the tiles that were never staged (past klen, or above the causal diagonal): exact zeros
+    for (int key = ntile * 64 + (threadIdx.x >> 3); key < p.Tk; key += 32) {
+        const int c = (threadIdx.x & 7) * 8;
+        *reinterpret_cast<u32x2*>(dKg + (long)key * p.dk_st + c) = (u32x2){0u, 0u};
+        *reinterpret_cast<u32x2*>(dKg + (long)key * p.dk_st + c + 4) = (u32x2){0u, 0u};
+        *reinterpret_cast<u32x2*>(dVg + (long)key * p.dv_st + c) = (u32x2){0u, 0u};
+        *reinterpret_cast<u32x2*>(dVg + (long)key * p.dv_st + c + 4) = (u32x2){0u, 0u};
+    }
+    // ---- dQ = scale * (sum over the waves, in wave order), 32 features at a time through the K/V buffers: [wave][64 queries][32] f32
+    float* red = reinterpret_cast<float*>(sKV);
+    bf16* dQg = reinterpret_cast<bf16*>(p.dQ) + (long)b * p.dq_sb + (long)h * DH;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        if (half) __syncthreads();                        // the first half's sums are read
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i >= nq) break;
+#pragma unroll
+            for (int nn = 0; nn < 2; ++nn)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) red[(wave * 64 + 16 * i + 4 * q + r) * 32 + 16 * nn + r16] = dq[i][2 * half + nn][r];
+        }
+        __syncthreads();
+        const int row = threadIdx.x >> 2, c = (threadIdx.x & 3) * 8;
+        if (row < p.Tq) {
+            f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                s0 += *reinterpret_cast<const f32x4*>(red + (w * 64 + row) * 32 + c);
+                s1 += *reinterpret_cast<const f32x4*>(red + (w * 64 + row) * 32 + c + 4);
+            }
+            s0 *= p.scale; s1 *= p.scale;
+            *reinterpret_cast<u32x2*>(dQg + (long)row * p.dq_st + 32 * half + c) = (u32x2){pack_bf16(s0[0], s0[1]), pack_bf16(s0[2], s0[3])};
+            *reinterpret_cast<u32x2*>(dQg + (long)row * p.dq_st + 32 * half + c + 4) = (u32x2){pack_bf16(s1[0], s1[1]), pack_bf16(s1[2], s1[3])};
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------ C ABI
 // the second-generation kernels address the rows of a staged tensor by 32-bit byte offsets built with a 24-bit multiply
 static bool span32(long stride, int rows) {
@@ -1175,6 +1581,25 @@ static bool strides_ok(int dtype, const long* s, int n) {
     const int e = dtype == S2T_BF16 ? 8 : 4;
     for (int i = 0; i < n; ++i) if (s[i] % e) return false;
     return true;
+}
+
+// Short-query route (attn_fwd_sq_kernel / attn_bwd_sq_kernel): bf16, d = 64 (the callers check), no distance penalty, Tq <= 64 and
+// either the cross-attention shape the second generation took before (Tq >= attn_v2_min_tq, Tk >= 128) or causal self-attention
+// with Tq == Tk; attn_v1 = 1 forces the first generation (the in-tree A/B switch), raising attn_v2_min_tq above Tq still sends a
+// cross-attention block there.  The dropout quad index is kept in one 32-bit word, K / V rows are addressed by 32-bit offsets.
+static bool sq_shape(const AttnArgs& a) {
+    if (g_s2t_opt_attn_v1 != 0 || a.dist_pen || a.Tq > 64) return false;
+    if (!((a.Tq >= S2T_ATTN_V2_MIN_TQ && a.Tk >= 128) || (a.causal && a.Tq == a.Tk))) return false;
+    const bool idx32 = (unsigned long long)a.B * a.H * a.Tq * (unsigned long long)((a.Tk + 3) & ~3) < (1ull << 34);
+    return idx32 && span32(a.k_st, a.Tk) && span32(a.v_st, a.Tk);
+}
+static bool sq_fwd_route(const AttnArgs& a) {
+    return sq_shape(a) && !(a.o_st % 4) && !(a.o_sb % 4) && !((uintptr_t)a.O & 7);
+}
+static bool sq_bwd_route(const AttnArgs& a) {
+    const bool al = !(a.dk_st % 4) && !(a.dk_sb % 4) && !(a.dv_st % 4) && !(a.dv_sb % 4) && !(a.dq_st % 4) && !(a.dq_sb % 4) &&
+                    !((uintptr_t)a.dK & 7) && !((uintptr_t)a.dV & 7) && !((uintptr_t)a.dQ & 7);
+    return sq_shape(a) && al && span32(a.q_st, a.Tq) && span32(a.do_st, a.Tq) && !(a.o_st % 8) && !(a.o_sb % 8) && !((uintptr_t)a.O & 15);
 }
 
 template <typename T, int DH> static int fwd_launch(const AttnArgs& a, hipStream_t st) {
@@ -1190,6 +1615,11 @@ template <typename T, int DH> static int bwd_launch(const AttnArgs& a, hipStream
     const long rows = (long)a.B * a.H * a.Tq;
     bool dkv2 = false, dq2 = false;
     if constexpr (sizeof(T) == 2 && DH == 64) {
+        if (sq_bwd_route(a)) {                           // one pass: Delta, dQ, dK and dV from one kernel
+            hipLaunchKernelGGL(attn_bwd_sq_kernel, dim3((unsigned)(a.B * a.H)), dim3(256), S2T_SQ_BWD_LDS, st, a);
+            S2T_LAUNCH_CHECK();
+            return S2T_OK;
+        }
         const bool v1 = g_s2t_opt_attn_v1 != 0;                            // s2t_set_option("attn_v1")
         const bool al = !(a.dk_st % 4) && !(a.dk_sb % 4) && !(a.dv_st % 4) && !(a.dv_sb % 4) && !(a.dq_st % 4) && !(a.dq_sb % 4) &&
                         !((uintptr_t)a.dK & 7) && !((uintptr_t)a.dV & 7) && !((uintptr_t)a.dQ & 7);
@@ -1265,6 +1695,11 @@ extern "C" int s2t_attn_fwd(int dtype, int head_dim, int B, int H, int Tq, int T
     if (!strides_ok(dtype, s, 6)) return S2T_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("attn_fwd", st, 4.0 * B * H * (double)Tq * Tk * head_dim * (causal ? 0.5 : 1.0), 0.0);
+    if (dtype == S2T_BF16 && head_dim == 64 && sq_fwd_route(a)) {
+        hipLaunchKernelGGL(attn_fwd_sq_kernel, dim3((unsigned)(B * H)), dim3(256), 32768 + 512 + 8192, st, a);
+        S2T_LAUNCH_CHECK();
+        return S2T_OK;
+    }
     if (dtype == S2T_BF16 && head_dim == 64 && (Tq >= 128 || (Tq >= S2T_ATTN_V2_MIN_TQ && Tk >= 128)) && (o_st % 4) == 0 && (o_sb % 4) == 0 && ((uintptr_t)O & 7) == 0) {
         const bool v1 = g_s2t_opt_attn_v1 != 0 || !span32(k_st, Tk) || !span32(v_st, Tk);     // s2t_set_option("attn_v1")
         if (!v1) {
@@ -1299,7 +1734,11 @@ extern "C" int s2t_attn_bwd(int dtype, int head_dim, int B, int H, int Tq, int T
     const long s[] = {q_st, q_sb, k_st, k_sb, v_st, v_sb, do_st, do_sb};
     if (!strides_ok(dtype, s, 8)) return S2T_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("attn_bwd", st, 14.0 * B * H * (double)Tq * Tk * head_dim * (causal ? 0.5 : 1.0), 0.0);
+    // issued FLOPs: the two-kernel routes make S and dP twice (14 B H Tq Tk d), the one-pass short-query route once (10).  bench.py
+    // rescales this family by 10 / 14 on the assumption of two recomputations, so the figure it reports for the short-query route is
+    // conservative (below the model FLOPs actually delivered).
+    const bool sq = dtype == S2T_BF16 && head_dim == 64 && sq_bwd_route(a);
+    ProfScope prof("attn_bwd", st, (sq ? 10.0 : 14.0) * B * H * (double)Tq * Tk * head_dim * (causal ? 0.5 : 1.0), 0.0);
     if (dtype == S2T_BF16) return head_dim == 64 ? bwd_launch<bf16, 64>(a, st) : bwd_launch<bf16, 32>(a, st);
     return head_dim == 64 ? bwd_launch<float, 64>(a, st) : bwd_launch<float, 32>(a, st);
 }
