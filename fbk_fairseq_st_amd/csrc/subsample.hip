@@ -1098,6 +1098,7 @@ extern "C" int s2t_conv2_wgrad(int dtype, const void* dpre, const void* y1n, flo
     if (!dpre || !y1n || !gw) return S2T_EINVAL;
     const int T4 = (T2 + 1) / 2, F4 = (F2 + 1) / 2;
     if (dtype != S2T_BF16 || C != 64 || F4 > 32 || F2 > 64 || 3 * F2 * 8 + F4 * 8 > 1280) return S2T_ENOTSUP;   // callers fall back to the gathered GEMMs
+    if (((uintptr_t)dpre | (uintptr_t)y1n) & 15) return S2T_ENOTSUP;         // 16-byte staging loads (as s2t_conv2_fwd / s2t_conv2_dgrad)
     const int ngroups = T4 * B;
     int gpw = (ngroups + 511) / 512;                            // 2 workgroups per CU
     gpw = gpw < 8 ? 8 : gpw;

@@ -994,6 +994,7 @@ def test_augment_kernel_reproduces_the_reference_batches():
         assert torch.equal(batch["net_input"]["src_tokens"].cpu(), torch.from_numpy(g["c%d_out" % ci])), ci
 
 
+# (the three direct conv2 kernels element by element against float64, their limits and refusals: tests/test_conv2_gpu.py)
 @pytest.mark.parametrize("B,T2,F2", [(3, 37, 40), (2, 10, 20), (5, 64, 40), (1, 1, 40)])
 def test_conv2_wgrad_all_taps_kernel(B, T2, F2):
     """s2t_conv2_wgrad (bf16, 64 channels) against torch's conv2d weight gradient in fp32: odd T2 (last output row sees one input

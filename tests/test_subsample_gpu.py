@@ -24,6 +24,7 @@ Error model (u = 2^-24; r = 2^-8 for a bf16 output, u for f32; gamma_n = n u / (
     magnitudes the kernel adds (subsample.hip:337,422), not |dpre|: kb y and kc cancel when |mean| >> std.  The activation derivative
     multiplies that by <= 1.13 and GELU's adds 8 u |r| <= 8 u M: e_p = 8 u M (ReLU), 18 u M (GELU).
 """
+import contextlib
 import math
 
 import pytest
@@ -84,6 +85,24 @@ def assert_close(out, ref, bound, what, kernel=None):
         raise AssertionError("%s: %d of %d elements out of bound; worst at %s: out %.9g ref %.9g |err| %.3g bound %.3g (%.3gx)"
                              % (what, int(bad.sum()), bad.numel(), idx, float(o[idx]), float(ref[idx]), float(err[idx]),
                                 float(bound[idx]), float(err[idx] / bound[idx]) if float(bound[idx]) > 0 else math.inf))
+
+
+@contextlib.contextmanager
+def launches(*families):
+    """launch counts of the given kernel families for everything run inside the block (the library's event-bracketed profiler)"""
+    from fbk_fairseq_st_amd import kernels as k      # (tests/test_conv2_gpu.py imports this helper: no use of this module's K)
+    counts = {}
+    torch.cuda.synchronize()
+    k.prof_reset()
+    k.prof_enable(1)
+    try:
+        yield counts
+    finally:
+        torch.cuda.synchronize()
+        for f in families:
+            counts[f] = k.prof_read(f)["launches"]
+        k.prof_enable(0)
+        k.prof_reset()
 
 
 def gen(seed):
@@ -636,18 +655,19 @@ def product_ref(X, W, bias):
     return acc, 4 * X.shape[1] * U * (X.abs() @ W.abs().t() + bias.abs())
 
 
-def check_act_out(out, pre, acc, e_acc, act, dtype, what):
+def check_act_out(out, pre, acc, e_acc, act, dtype, what, kernel="chain"):
     """out = act(acc) stored (and pre = acc stored for GELU).  GELU's value may come from the f32 accumulator or from the stored
-    pre-activation: the bound takes the rounding of pre (r |acc|) as one more input error, slope <= 1.13, and gelu_f's 8 u |x|."""
+    pre-activation: the bound takes the rounding of pre (r |acc|) as one more input error, slope <= 1.13, and gelu_f's 8 u |x|.
+    `kernel`: the name the worst ratio is recorded under (tests/test_conv2_gpu.py passes its own)."""
     r = rout(dtype)
     if act == "relu":
         ref = acc.clamp_min(0.0)
-        assert_close(out, ref, e_acc + r * (ref.abs() + e_acc), what, "chain")
+        assert_close(out, ref, e_acc + r * (ref.abs() + e_acc), what, kernel)
         return
-    assert_close(pre, acc, e_acc + r * (acc.abs() + e_acc), what + " pre", "chain")
+    assert_close(pre, acc, e_acc + r * (acc.abs() + e_acc), what + " pre", kernel)
     ref = gelu64(acc)
     e = 1.13 * (e_acc + r * (acc.abs() + e_acc)) + 8 * U * (acc.abs() + e_acc)
-    assert_close(out, ref, e + r * (ref.abs() + e), what, "chain")
+    assert_close(out, ref, e + r * (ref.abs() + e), what, kernel)
 
 
 def check_bn_stage(y, mean, rstd, gamma, beta, yn, bufs0, bufs, pfx, depth, dtype, what):
@@ -677,7 +697,8 @@ def check_bn_stage(y, mean, rstd, gamma, beta, yn, bufs0, bufs, pfx, depth, dtyp
 
 
 CHAIN = [(C, dtype, act, feat) for C in (32, 64, 128) for dtype in (F32, BF) for act, feat in (("relu", 80), ("gelu", 81))] + \
-        [(64, BF, "relu", 81), (64, BF, "gelu", 80)]
+        [(64, BF, "relu", 81), (64, BF, "gelu", 80)] + \
+        [(64, BF, act, feat) for feat in (89, 91, 95, 97) for act in ("relu", "gelu")]      # F2 = 45, 46, 48, 49: the direct kernels' limits
 
 
 @pytest.mark.parametrize("C,dtype,act,feat", CHAIN)
@@ -689,6 +710,11 @@ def test_subsample_chain_against_fp64(C, dtype, act, feat):
     the data gradient.  permute_conv_w mode 0 (w2p) is checked bit for bit; fc3's reference flattens channel-major with the master
     weight (conv_transformer.py:225-226), so a wrong permute_cf order fails h3, and modes 1 / 2 of the two permutes are checked
     through the gradients.
+    The three direct kernels have three limits: the forward takes F2 <= 48 (conv2.hip:142), the data gradient F2 <= 47 (conv2.hip:273),
+    the weight gradient F2 <= 45 (subsample.hip:1100), and the engine falls back per kernel.  feat = 89 / 91 / 95 / 97 (F2 = 45 / 46 /
+    48 / 49) run all three direct; the weight gradient gathered; only the forward direct; none direct -- a step that mixes direct and
+    gathered kernels on the same tensors.  Which route ran is asserted: conv2_fwd / conv2_dgrad record a launch family, the weight
+    gradient records none and is probed with a direct K.conv2_wgrad call at the step's geometry.
     Gradient bounds, normwise per parameter: f32, the README's parity contract 1e-3 of |g_ref|.  bf16: every stored activation (y1,
     y1n, z2, z2n, h3), both compute-dtype weights (w2p, w3p) and every stored gradient (dh3, dz2n, dpre2, dy1n) is rounded to bf16
     once: 12 roundings of relative size <= 2^-8 on the path to a gradient, 12 x 2^-8 = 0.047 -> 0.05, relative to the sums of
@@ -704,8 +730,11 @@ def test_subsample_chain_against_fp64(C, dtype, act, feat):
     len4 = ((lens + 1) // 2 + 1) // 2
     bufs0 = {k: v.clone() for k, v in eng.bn_buffers.items()}
     A.zero_grad()
-    xe, c = eng.subsample_fwd(x, len4.to(torch.int32).to(DEV), True, 5)
+    with launches("conv2_fwd", "gemm_gather") as ran:
+        xe, c = eng.subsample_fwd(x, len4.to(torch.int32).to(DEV), True, 5)
     T2, F2, T4, F4 = c["T2"], c["F2"], c["T4"], c["F4"]
+    direct = C == 64 and dtype == BF
+    assert (ran["conv2_fwd"], ran["gemm_gather"]) == ((1, 0) if direct and F2 <= 48 else (0, 1)), (F2, ran)
     what = "chain C=%d %s %s F=%d" % (C, dtype, act, feat)
     Pm = lambda n: A.p(n)
     # conv1 + BN1
@@ -737,9 +766,16 @@ def test_subsample_chain_against_fp64(C, dtype, act, feat):
     assert_close(xe, ref, e + rout(dtype) * (ref.abs() + e), what + " xe", "chain")
     # backward against float64 autograd of the reference subsampler
     dx = randn(T4 * B, model.hp.D, seed=1400 + C, dtype=dtype)
-    eng.subsample_bwd(c, dx)
-    eng.flush_wgrad()
-    torch.cuda.synchronize()
+    with launches("conv2_dgrad", "gemm_gather") as ran:
+        eng.subsample_bwd(c, dx)
+        eng.flush_wgrad()
+    wgrad_direct = K.conv2_wgrad(torch.zeros(T4 * B * F4, C, dtype=dtype, device=DEV), c["y1n"].view(-1, C),
+                                 torch.zeros(C, 9 * C, device=DEV), B, T2, F2, C)
+    assert wgrad_direct == (direct and F2 <= 45), (F2, wgrad_direct)
+    # gathered launches: nine per-tap products of the weight gradient, one per pixel-parity class of the data gradient
+    # (F2 >= 2 and T2 >= 2 here: all four classes have pixels)
+    want = ((1, 0) if direct and F2 <= 47 else (0, 4))
+    assert (ran["conv2_dgrad"], ran["gemm_gather"]) == (want[0], want[1] + (0 if wgrad_direct else 9)), (F2, ran)
     W = {n: A.p(n).detach().double().cpu().requires_grad_(True) for n in SUB}
     for n in ("encoder.bn.0.", "encoder.bn.1."):
         W[n + "running_mean"], W[n + "running_var"] = bufs0[n + "running_mean"].double().cpu(), bufs0[n + "running_var"].double().cpu()
