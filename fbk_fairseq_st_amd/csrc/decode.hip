@@ -996,14 +996,24 @@ struct RowArgs {
     const float* logits; const int* steps; const float* cum_hist; const float* init_scores; float* cand_val; int* cand_idx;
 };
 struct RowRuleArgs : RowArgs { int ngram, prefix_len, maxpos; const int* prefix; const int* tok_hist; const int* anc; };
-template <bool RULES> struct RowArgsOf { typedef RowArgs type; };
-template <> struct RowArgsOf<true> { typedef RowRuleArgs type; };
+// ENS (s2t_decode_step_ensemble, n >= 2 members; always with the RULES code, switched off by ngram = prefix_len = 0): the row's
+// log-probability is the log of the members' mean probability, as ensemble_lse_kernel of loss_embed.hip takes it (members in order:
+// m = max_j lp_j, -inf when m is, else m + logf(sum_j expf(lp_j - m)) - logf(n)), every lp_j the member's own log-softmax in the
+// arithmetic below.  Three passes over the members' logits rows (they sit in L2), each with the member as the OUTER loop so that a
+// pass requests a member's VPT columns together: the members' lse; the column maxima; the column sums.  2 VPT values in registers.
+constexpr int ENS_MAX = 8;
+struct RowEnsArgs : RowRuleArgs { int n_mem; float log_n; const float* mem[ENS_MAX]; };
+template <bool RULES, bool ENS = false> struct RowArgsOf { typedef RowArgs type; };
+template <> struct RowArgsOf<true, false> { typedef RowRuleArgs type; };
+template <> struct RowArgsOf<true, true> { typedef RowEnsArgs type; };
 constexpr int ROW_HIST = 1024;                                     // positions of a history (max_len + 1 <= 1024), and words of the ban bitmap (V <= 32768)
 __device__ __forceinline__ bool cand_after(float v, int i, float lv, int li) { return v < lv || (v == lv && i > li); }
 __device__ __forceinline__ bool cand_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-template <int VPT, bool RULES>
-__global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RULES>::type a) {
+template <int VPT, bool RULES, bool ENS = false>
+__global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RULES, ENS>::type a) {
+    static_assert(!ENS || RULES, "the ensemble row is built on the RULES variant");
     __shared__ float sh[16];
+    [[maybe_unused]] float* const lse_s = sh + 8;                    // ENS: the members' normalisers (the block reductions use sh[0 .. 3])
     __shared__ float wv[4 * 32];
     __shared__ int wi[4 * 32];
     __shared__ int g_s[RULES ? ROW_HIST : 1];
@@ -1036,7 +1046,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
             for (int i = tid; i < (V + 31) / 32; i += NTHREADS) ban_s[i] = 0u;
         }
     }
-    const float* x = a.logits + (size_t)n * a.ldv;
+    const float* x = a.logits + (size_t)n * a.ldv;                   // ENS: member 0's
     float val[VPT];
     float m = -INFINITY;
 #pragma unroll
@@ -1055,6 +1065,51 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
     }
     z = block_sum(z, sh);
     const float lse = m + logf(z);
+    if constexpr (ENS) {
+        const int nm = a.n_mem;
+        if (tid == 0) lse_s[0] = lse;
+        for (int j = 1; j < nm; ++j) {                               // the other members' normalisers, in the arithmetic above
+            const float* xj = a.mem[j] + (size_t)n * a.ldv;
+            float mj = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) {
+                const int v = tid + i * NTHREADS;
+                val[i] = xj[min(v, V - 1)] * a.it;
+                if (v >= V) val[i] = -INFINITY;
+                mj = fmaxf(mj, val[i]);
+            }
+            mj = block_max(mj, sh);
+            float zj = 0.f;
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) {
+                const int v = tid + i * NTHREADS;
+                if (v < V) zj += expf(val[i] - mj);
+            }
+            zj = block_sum(zj, sh);
+            if (tid == 0) lse_s[j] = mj + logf(zj);
+        }
+        __syncthreads();
+        // val[] = max_j lp_j, then sm[] = sum_j expf(lp_j - max), members in order; lp_j = x_j * it (rounded, as above) - lse_j
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) val[i] = -INFINITY;
+        for (int j = 0; j < nm; ++j) {
+            const float* xj = a.mem[j] + (size_t)n * a.ldv;
+            const float l = lse_s[j];
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) val[i] = fmaxf(val[i], __fmul_rn(xj[min(tid + i * NTHREADS, V - 1)], a.it) - l);
+        }
+        float sm[VPT];
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) sm[i] = 0.f;
+        for (int j = 0; j < nm; ++j) {
+            const float* xj = a.mem[j] + (size_t)n * a.ldv;
+            const float l = lse_s[j];
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) sm[i] += expf((__fmul_rn(xj[min(tid + i * NTHREADS, V - 1)], a.it) - l) - val[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) val[i] = val[i] > -INFINITY ? val[i] + logf(sm[i]) - a.log_n : -INFINITY;
+    }
     DSTAMP(3, 1);
     if constexpr (RULES) {
         if (blocking) {                                            // the same in every thread of the workgroup
@@ -1080,6 +1135,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
     for (int i = 0; i < VPT; ++i) {
         const int v = tid + i * NTHREADS;
         float lp = val[i] - lse;
+        if constexpr (ENS) lp = val[i];                            // already the log of the members' mean probability
         if (lp != lp) lp = -INFINITY;
         if (v == a.pad) lp = -INFINITY;
         if (v == a.unk) lp -= a.unk_penalty;
@@ -1214,8 +1270,19 @@ struct SentArgs {
     const float* cand_val; const int* cand_idx; int* steps; int* anc; int* tok_hist; int* par_hist; float* cum_hist; int* blacklist;
     int* nfin; int* finished; int* fin_step; int* fin_row; float* fin_score; const void* embed; const float* pos_table; float* x0;
 };
-template <typename T>
-__global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(SentArgs a) {
+// ENS: the other members' next input (member 0 is SentArgs' own), each from its own embedding, position table, D and scale
+struct SentMember { const void* embed; const float* pos_table; float* x0; int D; float embed_scale; };
+struct SentEnsArgs : SentArgs { int n_more; SentMember more[ENS_MAX - 1]; };
+template <bool ENS> struct SentArgsOf { typedef SentArgs type; };
+template <> struct SentArgsOf<true> { typedef SentEnsArgs type; };
+__device__ __forceinline__ int ens_more(const SentArgs&) { return 0; }
+__device__ __forceinline__ int ens_more(const SentEnsArgs& a) { return a.n_more; }
+__device__ __forceinline__ SentMember ens_member(const SentArgs& a, int) { return SentMember{a.embed, a.pos_table, a.x0, a.D, a.embed_scale}; }
+__device__ __forceinline__ SentMember ens_member(const SentEnsArgs& a, int j) {
+    return j == 0 ? SentMember{a.embed, a.pos_table, a.x0, a.D, a.embed_scale} : a.more[j - 1];
+}
+template <typename T, bool ENS = false>
+__global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<ENS>::type a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ __attribute__((aligned(16))) float l_val[16 * 32];
     __shared__ __attribute__((aligned(16))) int l_idx[16 * 32];
@@ -1307,24 +1374,28 @@ __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(SentArgs a) {
     if (t < a.max_len) {
         // the next step's decoder input: embedding of the chosen token * scale + position row (transformer.py:720-737), four columns per
         // item, four items per thread requested together (all of beam 5 x D 512 in one round trip)
-        const int dq = a.D / 4, items = beam * dq;
-        for (int i0 = 0; i0 < items; i0 += 4 * NTHREADS) {
-            f32x4 ev4[4], pv4[4];
+        // ENS: the same for every member, member 0 (SentArgs' own fields) first
+        for (int mj = 0; mj < (ENS ? 1 + ens_more(a) : 1); ++mj) {
+            const SentMember me = ens_member(a, mj);
+            const int dq = me.D / 4, items = beam * dq;
+            for (int i0 = 0; i0 < items; i0 += 4 * NTHREADS) {
+                f32x4 ev4[4], pv4[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = min(i0 + u * NTHREADS + tid, items - 1), j = i / dq, d = (i - j * dq) * 4;
-                const int tok = pick_tok[j];
-                ev4[u] = Raw4<T>::cvt(Raw4<T>::ld(reinterpret_cast<const T*>(a.embed) + (size_t)tok * a.D + d));
-                pv4[u] = *reinterpret_cast<const f32x4*>(a.pos_table + (size_t)(tok == a.pad ? a.pad : a.pad + 2 + t) * a.D + d);
-            }
+                for (int u = 0; u < 4; ++u) {
+                    const int i = min(i0 + u * NTHREADS + tid, items - 1), j = i / dq, d = (i - j * dq) * 4;
+                    const int tok = pick_tok[j];
+                    ev4[u] = Raw4<T>::cvt(Raw4<T>::ld(reinterpret_cast<const T*>(me.embed) + (size_t)tok * me.D + d));
+                    pv4[u] = *reinterpret_cast<const f32x4*>(me.pos_table + (size_t)(tok == a.pad ? a.pad : a.pad + 2 + t) * me.D + d);
+                }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * NTHREADS + tid, j = i / dq, d = (i - j * dq) * 4;
-                if (i < items) {
-                    f32x4 o;
+                for (int u = 0; u < 4; ++u) {
+                    const int i = i0 + u * NTHREADS + tid, j = i / dq, d = (i - j * dq) * 4;
+                    if (i < items) {
+                        f32x4 o;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = a.embed_scale * ev4[u][q] + pv4[u][q];
-                    *reinterpret_cast<f32x4*>(a.x0 + (size_t)(n0 + j) * a.D + d) = o;
+                        for (int q = 0; q < 4; ++q) o[q] = me.embed_scale * ev4[u][q] + pv4[u][q];
+                        *reinterpret_cast<f32x4*>(me.x0 + (size_t)(n0 + j) * me.D + d) = o;
+                    }
                 }
             }
         }
@@ -1449,7 +1520,7 @@ template <typename T> hipError_t configure() {
         if ((e = configure_dd<T, 256>()) != hipSuccess) return e;
         if ((e = configure_dd<T, 512>()) != hipSuccess) return e;
     }
-    DEC_ALLOW(dec_sent_kernel<T>);
+    DEC_ALLOW(dec_sent_kernel<T>); DEC_ALLOW((dec_sent_kernel<T, true>));
     DEC_ALLOW((dec_logits_kernel<T, 1>)); DEC_ALLOW((dec_logits_kernel<T, 2>)); DEC_ALLOW((dec_logits_kernel<T, 3>)); DEC_ALLOW((dec_logits_kernel<T, 4>));
     DEC_ALLOW((dec_logits_kernel<T, 5>)); DEC_ALLOW((dec_logits_kernel<T, 6>)); DEC_ALLOW((dec_logits_kernel<T, 7>)); DEC_ALLOW((dec_logits_kernel<T, 8>));
     return hipSuccess;
@@ -1480,11 +1551,11 @@ void launch_ffn(int hs, dim3 grid, size_t lds, hipStream_t st, const FfnArgs& a)
 }  // namespace
 int g_s2t_opt_decode_stop_after = 0;      // diagnostic (s2t_set_option "decode_stop_after"): > 0 ends a step after that many launches
 namespace {
-#define DEC_STOP_CHECK() do { if (g_s2t_opt_decode_stop_after > 0 && ++launched >= g_s2t_opt_decode_stop_after) { S2T_LAUNCH_CHECK(); return S2T_OK; } } while (0)
-// r: the rules of s2t_decode_step_rules, or NULL (checked by rules_check)
+constexpr int DEC_STOPPED = 1;           // chain_impl: the decode_stop_after diagnostic ended the step
+#define DEC_STOP_CHECK() do { if (g_s2t_opt_decode_stop_after > 0 && ++launched >= g_s2t_opt_decode_stop_after) { S2T_LAUNCH_CHECK(); return DEC_STOPPED; } } while (0)
+// one model's launches up to its logits (3 * layers + 2); `launched` counts for decode_stop_after, across the members of an ensemble
 template <typename T>
-int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
-    int launched = 0;
+int chain_impl(const S2TDecodeDesc* d, hipStream_t st, int& launched) {
     const int B = d->B, R = d->beam, N = B * R, D = d->D, H = d->heads, FS = d->ffn_slices, hs = d->ffn / FS, maxpos = d->max_len + 1;
     const LdsNeed need = lds_need(d);
     float* X[2] = {d->x0, d->x1};
@@ -1547,31 +1618,89 @@ int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
 #undef DEC_LOGITS
         DEC_STOP_CHECK();
     }
+    return S2T_OK;
+}
+void row_args(const S2TDecodeDesc* d, const S2TDecodeRules* r, bool rules, RowRuleArgs& a) {
+    const int R = d->beam;
+    a.beam = R; a.N = d->B * R; a.V = d->V; a.ldv = d->ldv; a.K2 = 2 * R; a.pad = d->pad; a.unk = d->unk; a.eos = d->eos;
+    a.max_len = d->max_len; a.min_len = d->min_len; a.step0_all = d->step0_all_slots; a.it = d->inv_temperature; a.unk_penalty = d->unk_penalty;
+    a.logits = d->logits; a.steps = d->steps; a.cum_hist = d->cum_hist; a.init_scores = d->init_scores; a.cand_val = d->cand_val;
+    a.cand_idx = d->cand_idx;
+    a.ngram = rules ? r->no_repeat_ngram : 0; a.prefix_len = rules ? r->prefix_len : 0; a.prefix = rules ? r->prefix : nullptr;
+    a.maxpos = d->max_len + 1; a.tok_hist = d->tok_hist; a.anc = d->anc;
+}
+void sent_args(const S2TDecodeDesc* d, SentArgs& a) {
+    const int R = d->beam;
+    a.beam = R; a.N = d->B * R; a.D = d->D; a.V = d->V; a.K2 = 2 * R; a.pad = d->pad; a.eos = d->eos; a.max_len = d->max_len; a.maxpos = d->max_len + 1;
+    a.step0_all = d->step0_all_slots; a.embed_scale = d->embed_scale; a.cand_val = d->cand_val; a.cand_idx = d->cand_idx; a.steps = d->steps;
+    a.anc = d->anc; a.tok_hist = d->tok_hist; a.par_hist = d->par_hist; a.cum_hist = d->cum_hist; a.blacklist = d->blacklist; a.nfin = d->nfin;
+    a.finished = d->finished; a.fin_step = d->fin_step; a.fin_row = d->fin_row; a.fin_score = d->fin_score; a.embed = d->embed;
+    a.pos_table = d->pos_table; a.x0 = d->x0;
+}
+// columns per thread of the row launch: the kernel is bound by its per-column VALU work on a wave that runs alone on its SIMD, so the
+// unrolled loops are sized to the vocabulary (V = 5,000: 20, not 32)
+#define DEC_ROW_BY_VPT(V_) do { const int vpt = ((V_) + NTHREADS - 1) / NTHREADS; \
+        if (vpt <= 8) DEC_ROW(8); else if (vpt <= 12) DEC_ROW(12); else if (vpt <= 16) DEC_ROW(16); else if (vpt <= 20) DEC_ROW(20); \
+        else if (vpt <= 24) DEC_ROW(24); else if (vpt <= 32) DEC_ROW(32); else if (vpt <= 40) DEC_ROW(40); else if (vpt <= 48) DEC_ROW(48); \
+        else if (vpt <= 64) DEC_ROW(64); else if (vpt <= 96) DEC_ROW(96); else DEC_ROW(128); } while (0)
+// r: the rules of s2t_decode_step_rules, or NULL (checked by rules_check)
+template <typename T>
+int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
+    int launched = 0;
+    const int rc = chain_impl<T>(d, st, launched);
+    if (rc != S2T_OK) return rc == DEC_STOPPED ? S2T_OK : rc;
+    const int B = d->B, N = B * d->beam;
+    const LdsNeed need = lds_need(d);
     {
-        RowRuleArgs a; a.beam = R; a.N = N; a.V = d->V; a.ldv = d->ldv; a.K2 = 2 * R; a.pad = d->pad; a.unk = d->unk; a.eos = d->eos;
-        a.max_len = d->max_len; a.min_len = d->min_len; a.step0_all = d->step0_all_slots; a.it = d->inv_temperature; a.unk_penalty = d->unk_penalty;
-        a.logits = d->logits; a.steps = d->steps; a.cum_hist = d->cum_hist; a.init_scores = d->init_scores; a.cand_val = d->cand_val;
-        a.cand_idx = d->cand_idx;
-        // columns per thread: the kernel is bound by its per-column VALU work on a wave that runs alone on its SIMD, so the unrolled loops
-        // are sized to the vocabulary (V = 5,000: 20, not 32)
+        RowRuleArgs a;
         const bool rules = r && (r->no_repeat_ngram > 0 || r->prefix_len > 0);
-        a.ngram = rules ? r->no_repeat_ngram : 0; a.prefix_len = rules ? r->prefix_len : 0; a.prefix = rules ? r->prefix : nullptr;
-        a.maxpos = maxpos; a.tok_hist = d->tok_hist; a.anc = d->anc;
+        row_args(d, r, rules, a);
 #define DEC_ROW(VPT_) do { if (rules) hipLaunchKernelGGL((dec_row_kernel<VPT_, true>), dim3(N), dim3(NTHREADS), 0, st, a); \
                            else hipLaunchKernelGGL((dec_row_kernel<VPT_, false>), dim3(N), dim3(NTHREADS), 0, st, static_cast<const RowArgs&>(a)); } while (0)
-        const int vpt = (d->V + NTHREADS - 1) / NTHREADS;
-        if (vpt <= 8) DEC_ROW(8); else if (vpt <= 12) DEC_ROW(12); else if (vpt <= 16) DEC_ROW(16); else if (vpt <= 20) DEC_ROW(20);
-        else if (vpt <= 24) DEC_ROW(24); else if (vpt <= 32) DEC_ROW(32); else if (vpt <= 40) DEC_ROW(40); else if (vpt <= 48) DEC_ROW(48);
-        else if (vpt <= 64) DEC_ROW(64); else if (vpt <= 96) DEC_ROW(96); else DEC_ROW(128);
+        DEC_ROW_BY_VPT(d->V);
 #undef DEC_ROW
     }
     {
-        SentArgs a; a.beam = R; a.N = N; a.D = D; a.V = d->V; a.K2 = 2 * R; a.pad = d->pad; a.eos = d->eos; a.max_len = d->max_len; a.maxpos = maxpos;
-        a.step0_all = d->step0_all_slots; a.embed_scale = d->embed_scale; a.cand_val = d->cand_val; a.cand_idx = d->cand_idx; a.steps = d->steps;
-        a.anc = d->anc; a.tok_hist = d->tok_hist; a.par_hist = d->par_hist; a.cum_hist = d->cum_hist; a.blacklist = d->blacklist; a.nfin = d->nfin;
-        a.finished = d->finished; a.fin_step = d->fin_step; a.fin_row = d->fin_row; a.fin_score = d->fin_score; a.embed = d->embed;
-        a.pos_table = d->pos_table; a.x0 = d->x0;
+        SentArgs a;
+        sent_args(d, a);
         hipLaunchKernelGGL(dec_sent_kernel<T>, dim3(B), dim3(NTHREADS), need.sent, st, a);
+    }
+    S2T_LAUNCH_CHECK();
+    return S2T_OK;
+}
+
+// One step of an ensemble of n >= 2 members (checked by ensemble_check: one search state, one dtype): every member's chain into its own
+// buffers, one after the other on `st`, then ONE row launch over all the members' logits and ONE sentence launch that also writes every
+// member's next input.  The serial order is what makes the shared `steps` and `anc` safe: no member's chain runs beside the sentence launch.
+template <typename T>
+int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, hipStream_t st) {
+    int launched = 0;
+    for (int j = 0; j < n; ++j) {
+        const int rc = chain_impl<T>(dv[j], st, launched);
+        if (rc != S2T_OK) return rc == DEC_STOPPED ? S2T_OK : rc;
+    }
+    const S2TDecodeDesc* d = dv[0];
+    const int B = d->B, N = B * d->beam;
+    {
+        RowEnsArgs a;
+        const bool rules = r && (r->no_repeat_ngram > 0 || r->prefix_len > 0);
+        row_args(d, r, rules, a);
+        a.n_mem = n; a.log_n = logf((float)n);
+        for (int j = 0; j < ENS_MAX; ++j) a.mem[j] = j < n ? dv[j]->logits : nullptr;
+#define DEC_ROW(VPT_) hipLaunchKernelGGL((dec_row_kernel<VPT_, true, true>), dim3(N), dim3(NTHREADS), 0, st, a)
+        DEC_ROW_BY_VPT(d->V);
+#undef DEC_ROW
+    }
+    {
+        SentEnsArgs a;
+        sent_args(d, a);
+        a.n_more = n - 1;
+        for (int j = 1; j < ENS_MAX; ++j) {
+            SentMember& o = a.more[j - 1];
+            if (j < n) { o.embed = dv[j]->embed; o.pos_table = dv[j]->pos_table; o.x0 = dv[j]->x0; o.D = dv[j]->D; o.embed_scale = dv[j]->embed_scale; }
+            else { o.embed = nullptr; o.pos_table = nullptr; o.x0 = nullptr; o.D = 0; o.embed_scale = 0.f; }
+        }
+        hipLaunchKernelGGL((dec_sent_kernel<T, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, a);
     }
     S2T_LAUNCH_CHECK();
     return S2T_OK;
@@ -1645,6 +1774,49 @@ extern "C" int s2t_decode_step_rules(const S2TDecodeDesc* d, const S2TDecodeRule
 }
 extern "C" int s2t_decode_step(const S2TDecodeDesc* d, void* stream) { return s2t_decode_step_rules(d, nullptr, stream); }
 
+// the checks of the *_ensemble calls, in the order include/s2t_hip.h documents
+static int ensemble_check(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r) {
+    if (!dv || n < 1 || n > ENS_MAX) return S2T_EINVAL;
+    for (int j = 0; j < n; ++j) if (!dv[j]) return S2T_EINVAL;
+    int rc = rules_check(r);
+    if (rc != S2T_OK) return rc;
+    const S2TDecodeDesc* a = dv[0];
+    for (int j = 1; j < n; ++j) {
+        const S2TDecodeDesc* b = dv[j];
+        if (a->dtype != b->dtype || a->B != b->B || a->beam != b->beam || a->V != b->V || a->ldv != b->ldv || a->max_len != b->max_len ||
+            a->min_len != b->min_len || a->pad != b->pad || a->unk != b->unk || a->eos != b->eos || a->step0_all_slots != b->step0_all_slots ||
+            a->unk_penalty != b->unk_penalty || a->inv_temperature != b->inv_temperature)
+            return S2T_EINVAL;
+        if (a->steps != b->steps || a->anc != b->anc || a->tok_hist != b->tok_hist || a->par_hist != b->par_hist || a->cum_hist != b->cum_hist ||
+            a->blacklist != b->blacklist || a->nfin != b->nfin || a->finished != b->finished || a->fin_step != b->fin_step ||
+            a->fin_row != b->fin_row || a->fin_score != b->fin_score || a->cand_val != b->cand_val || a->cand_idx != b->cand_idx ||
+            a->init_scores != b->init_scores)
+            return S2T_EINVAL;
+    }
+    for (int j = 0; j < n; ++j) if ((rc = decode_check(dv[j])) != S2T_OK) return rc;
+    return S2T_OK;
+}
+template <typename T>
+static int step_any(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, hipStream_t st) {
+    return n == 1 ? step_impl<T>(dv[0], r, st) : step_ens_impl<T>(dv, n, r, st);
+}
+
+extern "C" int s2t_decode_begin_ensemble(const S2TDecodeDesc* const* dv, int n, int bos, void* stream) {
+    const int rc = ensemble_check(dv, n, nullptr);
+    if (rc != S2T_OK) return rc;
+    if (bos < 0 || bos >= dv[0]->V) return S2T_EINVAL;
+    for (int j = 0; j < n; ++j) {                          // every member writes its own x0; the shared state is reset n times to the same values
+        const int rj = dv[j]->dtype == S2T_BF16 ? begin_impl<bf16>(dv[j], bos, (hipStream_t)stream) : begin_impl<float>(dv[j], bos, (hipStream_t)stream);
+        if (rj != S2T_OK) return rj;
+    }
+    return S2T_OK;
+}
+extern "C" int s2t_decode_step_ensemble(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, void* stream) {
+    const int rc = ensemble_check(dv, n, r);
+    if (rc != S2T_OK) return rc;
+    return dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, (hipStream_t)stream) : step_any<float>(dv, n, r, (hipStream_t)stream);
+}
+
 extern "C" int s2t_decode_prepare_enc(int dtype, const void* kv_enc, void* kp_enc, void* vp_enc, int Ts, int Tsp, int B, int D, int heads, void* stream) {
     if (!kv_enc || !kp_enc || !vp_enc || Ts < 1 || Tsp < Ts || Tsp % 128 || B < 1 || heads < 1 || D != heads * DH) return S2T_EINVAL;
     const size_t total = (size_t)2 * B * heads * Tsp * DH / (dtype == S2T_BF16 ? 8 : 4);
@@ -1670,14 +1842,8 @@ extern "C" int s2t_decode_pack_weight(int dtype, const void* W, int ldw, int N, 
     return S2T_OK;
 }
 
-extern "C" int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
-    if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
-    *graph_exec = nullptr;
-    if (!d) return S2T_EINVAL;
-    int rc = rules_check(r);
-    if (rc != S2T_OK) return rc;
-    rc = decode_check(d);
-    if (rc != S2T_OK) return rc;
+// n_steps x step_any(dv, n, r) recorded on a private stream as one chain and instantiated; the arguments are checked by the callers
+static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
     hipStream_t cs = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
     if (e != hipSuccess) return S2T_EHIP(e);
@@ -1686,7 +1852,7 @@ extern "C" int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDe
     int out = S2T_OK;
     e = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed);
     if (e == hipSuccess) {
-        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = d->dtype == S2T_BF16 ? step_impl<bf16>(d, r, cs) : step_impl<float>(d, r, cs);
+        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, cs) : step_any<float>(dv, n, r, cs);
         e = hipStreamEndCapture(cs, &g);
     }
     if (e == hipSuccess && out == S2T_OK) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
@@ -1696,6 +1862,23 @@ extern "C" int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDe
     if (e != hipSuccess) return S2T_EHIP(e);
     *graph_exec = ex;
     return S2T_OK;
+}
+extern "C" int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
+    if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
+    *graph_exec = nullptr;
+    if (!d) return S2T_EINVAL;
+    int rc = rules_check(r);
+    if (rc != S2T_OK) return rc;
+    rc = decode_check(d);
+    if (rc != S2T_OK) return rc;
+    return graph_record(&d, 1, r, n_steps, graph_exec);
+}
+extern "C" int s2t_decode_graph_create_ensemble(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
+    if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
+    *graph_exec = nullptr;
+    const int rc = ensemble_check(dv, n, r);
+    if (rc != S2T_OK) return rc;
+    return graph_record(dv, n, r, n_steps, graph_exec);
 }
 extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec) {
     return s2t_decode_graph_create_rules(d, nullptr, n_steps, graph_exec);

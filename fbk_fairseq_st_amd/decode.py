@@ -1,4 +1,4 @@
-"""Device-resident beam search over one incremental decoder.
+"""Device-resident beam search over one incremental decoder, or over an ensemble of up to eight.
 
 The search loop of the reference (fairseq/sequence_generator.py:243-447 with fairseq/search.py:55-83 and the incremental
 TransformerDecoder, fairseq/models/transformer.py:674-782) as `3 * layers + 4` kernel launches per decoding step, all of them
@@ -7,10 +7,15 @@ and looks at the `finished` flags every few steps.  Nothing of the state is re-o
 an ancestor table, the encoder-side K/V exist once per sentence, and the hypotheses are read back at the end by walking the
 recorded (token, parent, cumulative score) triples.
 
-`SequenceGenerator` (sequence_generator.py) takes this path for one model with the plain or the hierarchical beam search, with
-n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch (`s2t_decode_step_rules`),
-and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for ensembles, attention output, a prefix
-that holds EOS and n-gram size 1.
+An ensemble (`EnsembleDecodeSession`, `s2t_decode_*_ensemble`) shares ONE search state: every member runs its own launches up to its
+logits into its own buffers, one member after the other, then one row launch takes the log of the members' mean probability before the
+score rules and one sentence launch does the bookkeeping and embeds the chosen tokens for every member:
+`sum_j (3 * layers_j + 2) + 2` launches per step.  The members may differ in width, depth and encoder length.
+
+`SequenceGenerator` (sequence_generator.py) takes this path for one model or an ensemble with the plain or the hierarchical beam
+search, with n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch
+(`s2t_decode_step_rules`), and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for attention output,
+a prefix that holds EOS, n-gram size 1, members of different dtypes and any member outside the shape limits.
 """
 import ctypes
 import os
@@ -35,32 +40,41 @@ def _pick_hidden_slice(ffn, B):
     return 0
 
 
-class BeamDecodeSession:
-    """State + launch sequence of one beam search.  enc_out [Ts, B, D] (one column per SENTENCE), enc_klen int32 [B] or None.
-    no_repeat_ngram_size: 0 (off) or >= 2 (1 is refused: `ok` False); prefix_tokens: integer [B, P], pad = free, WITHOUT EOS (the
-    caller checks: sequence_generator._device_search) -- the session keeps its int32 device copy alive for the recorded graph."""
+class _Member:
+    """One model's share of a search: its descriptor, its buffers (`bufs`: x0, x1, part0, part1, xn, logits, cache<l>), its packed
+    weights and its encoder-side K/V.  `sh`: the scalars every member shares.  `ok` False: outside the limits of csrc/decode.hip
+    (nothing is allocated before `fill`)."""
 
-    def __init__(self, engine, pfx, enc_out, enc_klen, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0,
-                 init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None):
+    def __init__(self, engine, pfx, enc_out, enc_klen, sh):
         hp = engine.hp
         Ts, B, D = enc_out.shape
-        self.engine, self.B, self.beam, self.N, self.max_len = engine, B, beam, B * beam, max_len
-        self.pad, self.eos = pad, eos
-        dev, dtype = engine.dev, engine.dtype
-        N, H, Ff, Ld = self.N, hp.heads, hp.ffn, hp.dec_layers
-        Tsp = (Ts + 127) // 128 * 128
-        hs = _pick_hidden_slice(Ff, B)
-        ngram = max(int(no_repeat_ngram_size), 0)
-        self.rules, self.rules_addr = None, None                        # S2TDecodeRules when a rule beyond the descriptor's is set
-        self.ok = hs > 0 and ngram != 1
+        self.engine, self.pfx, self.enc_out, self.enc_klen = engine, pfx, enc_out, enc_klen
+        self.bufs, self.keep = {}, []
+        hs = _pick_hidden_slice(hp.ffn, B)
+        self.ok = hs > 0
         if not self.ok:
             return
-        FS = Ff // hs
+        beam, max_len, V, dtype = sh["beam"], sh["max_len"], sh["V"], engine.dtype
+        d = self.desc = L.DecodeDesc()
+        d.dtype, d.B, d.beam, d.D, d.heads, d.ffn, d.layers, d.V, d.ldv = (L.F32 if dtype == torch.float32 else L.BF16, B, beam, D, hp.heads, hp.ffn,
+                                                                           hp.dec_layers, V, V)
+        d.Ts, d.Tsp, d.max_len, d.min_len, d.ffn_slices, d.gelu = Ts, (Ts + 127) // 128 * 128, max_len, sh["min_len"], hp.ffn // hs, int(hp.act == "gelu")
+        d.pad, d.unk, d.eos, d.step0_all_slots = sh["pad"], sh["unk"], sh["eos"], int(bool(sh["step0_all_slots"]))
+        d.ln_eps, d.embed_scale = hp.ln_eps, 1.0 if hp.no_scale_embedding else float(D) ** 0.5
+        d.unk_penalty, d.inv_temperature = float(sh["unk_penalty"]), 1.0 / float(sh["temperature"])
+        self.layers = (L.DecodeLayer * hp.dec_layers)()
+        d.layer = ctypes.addressof(self.layers)
+        self.addr = ctypes.addressof(d)
+        self.ok = 0 < L.load().s2t_decode_lds_bytes(self.addr) <= LDS_CAP       # shape limits of csrc/decode.hip: checked before anything is allocated
+
+    def fill(self):
+        """buffers, packed weights and the encoder-side K/V"""
+        engine, pfx, d, keep = self.engine, self.pfx, self.desc, self.keep
+        hp, dev, dtype = engine.hp, engine.dev, engine.dtype
+        Ts, B, D = self.enc_out.shape
+        N, H, Ld, V, Tsp, FS, max_len, pad = B * d.beam, hp.heads, hp.dec_layers, d.V, d.Tsp, d.ffn_slices, d.max_len, d.pad
         lib = L.load()
         st = L.stream()
-        keep = self._keep = []
-
-        self.bufs = {}
 
         def dev_t(shape, dt, name=None):
             t = torch.empty(shape, dtype=dt, device=dev)
@@ -68,58 +82,14 @@ class BeamDecodeSession:
             if name:
                 self.bufs[name] = t                          # by name for tools/decode_debug.py and the tests
             return t
-        d = self.desc = L.DecodeDesc()
-        d.dtype, d.B, d.beam, d.D, d.heads, d.ffn, d.layers, d.V, d.ldv = L.F32 if dtype == torch.float32 else L.BF16, B, beam, D, H, Ff, Ld, V, V
-        d.Ts, d.Tsp, d.max_len, d.min_len, d.ffn_slices, d.gelu = Ts, Tsp, max_len, min_len, FS, int(hp.act == "gelu")
-        d.pad, d.unk, d.eos, d.step0_all_slots = pad, unk, eos, int(bool(step0_all_slots))
-        d.ln_eps, d.embed_scale = hp.ln_eps, 1.0 if hp.no_scale_embedding else float(D) ** 0.5
-        d.unk_penalty, d.inv_temperature = float(unk_penalty), 1.0 / float(temperature)
-        self.layers = (L.DecodeLayer * Ld)()
-        d.layer = ctypes.addressof(self.layers)
-        self.addr = ctypes.addressof(d)
-        self.ok = 0 < lib.s2t_decode_lds_bytes(self.addr) <= LDS_CAP         # shape limits of csrc/decode.hip: checked before anything is allocated
-        if not self.ok:
-            return
-        # state: one int32 and one float32 block, so that the read-back at the end is two copies
-        M2 = max_len + 2
-        isz = dict(tok_hist=M2 * N, par_hist=M2 * N, fin_step=B * beam, fin_row=B * beam, nfin=B, finished=B, steps=B, blacklist=N,
-                   anc=N * (max_len + 1), cand_idx=N * 2 * beam)
-        fsz = dict(cum_hist=M2 * N, fin_score=B * beam, cand_val=N * 2 * beam)
-        self.ibuf = dev_t((sum(isz.values()),), torch.int32)
-        self.fbuf = dev_t((sum(fsz.values()),), torch.float32)
-        self.ioff, self.foff = {}, {}
-        o = 0
-        for k, n in isz.items():
-            self.ioff[k] = (o, n); setattr(d, k, self.ibuf.data_ptr() + 4 * o); o += n
-        o = 0
-        for k, n in fsz.items():
-            self.foff[k] = (o, n); setattr(d, k, self.fbuf.data_ptr() + 4 * o); o += n
-        self.read_i = self.ioff["steps"][0]               # [tok_hist | par_hist | fin_step | fin_row | nfin | finished] come first
-        self.read_f = self.foff["cand_val"][0]
         d.x0, d.x1 = dev_t((N, D), torch.float32, "x0").data_ptr(), dev_t((N, D), torch.float32, "x1").data_ptr()
         np_max = max(H, FS)
         d.part0, d.part1 = dev_t((np_max, N, D), dtype, "part0").data_ptr(), dev_t((np_max, N, D), dtype, "part1").data_ptr()
         d.xn = dev_t((N, D), dtype, "xn").data_ptr()
         d.logits = dev_t((N, V), torch.float32, "logits").data_ptr()
-        if enc_klen is not None:
-            keep.append(enc_klen)
-            d.enc_klen = enc_klen.data_ptr()
-        if init_scores is not None:
-            init_scores = init_scores.to(device=dev, dtype=torch.float32).contiguous().view(-1)
-            assert init_scores.numel() == N
-            keep.append(init_scores)
-            d.init_scores = init_scores.data_ptr()
-        if prefix_tokens is not None and prefix_tokens.numel() == 0:
-            prefix_tokens = None
-        if ngram or prefix_tokens is not None:
-            r = self.rules = L.DecodeRules()
-            r.no_repeat_ngram = ngram
-            if prefix_tokens is not None:
-                assert prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == B
-                self.prefix = prefix_tokens.to(device=dev, dtype=torch.int32).contiguous()
-                keep.append(self.prefix)
-                r.prefix_len, r.prefix = self.prefix.shape[1], self.prefix.data_ptr()
-            self.rules_addr = ctypes.addressof(r)
+        if self.enc_klen is not None:
+            keep.append(self.enc_klen)
+            d.enc_klen = self.enc_klen.data_ptr()
         W, P = engine.W, engine.P
         ptr = lambda t: (keep.append(t), t.data_ptr())[1]
 
@@ -135,7 +105,7 @@ class BeamDecodeSession:
         d.w_out = packed(engine.out_proj(pfx) + ".weight")
         d.embed = ptr(W(pfx + "embed_tokens.weight"))
         d.pos_table = ptr(engine.table(pad + 3 + max_len, pad))
-        enc2d = enc_out.reshape(Ts * B, D)
+        enc2d = self.enc_out.reshape(Ts * B, D)
         for l in range(Ld):
             lp = pfx + "layers.%d." % l
             y = self.layers[l]
@@ -150,7 +120,88 @@ class BeamDecodeSession:
             keep.append(kv)
             y.kv_enc, y.vt_enc = kp.data_ptr(), vp.data_ptr()
             y.kv_cache = dev_t((max_len + 1, N, 2 * D), dtype, "cache%d" % l).data_ptr()
-        self.launches_per_step = 3 * Ld + 4
+
+
+class EnsembleDecodeSession:
+    """State + launch sequence of one beam search over 1..8 models that share the target dictionary (the reference's EnsembleModel,
+    fairseq/sequence_generator.py:711-770).  members: [(engine, pfx, enc_out, enc_klen), ...] -- enc_out [Ts_j, B, D_j] (one column per
+    SENTENCE), enc_klen int32 [B] or None; the members may differ in everything of their own (width, depth, encoder length) and must
+    have one compute dtype.  The search state (records, candidates, ancestor table, step counters) exists ONCE and every member's
+    descriptor names it; `members[j].bufs` / `bufs_of[j]` are member j's own buffers.  `ok` False: a member, the rules or the
+    combination is refused and nothing ran.  The other arguments as BeamDecodeSession's."""
+
+    def __init__(self, members, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0, init_scores=None,
+                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None):
+        members = list(members)
+        assert members, "an ensemble needs at least one member"
+        engine, enc_out = members[0][0], members[0][2]
+        B = enc_out.shape[1]
+        self.engine, self.B, self.beam, self.N, self.max_len = engine, B, beam, B * beam, max_len
+        self.pad, self.eos = pad, eos
+        dev = engine.dev
+        N = self.N
+        ngram = max(int(no_repeat_ngram_size), 0)
+        self.rules, self.rules_addr = None, None                        # S2TDecodeRules when a rule beyond the descriptor's is set
+        self.members = []
+        self.ok = ngram != 1 and 1 <= len(members) <= 8 and all(m[0].dtype == engine.dtype and m[2].shape[1] == B for m in members)
+        if not self.ok:
+            return
+        sh = dict(beam=beam, max_len=max_len, min_len=min_len, pad=pad, unk=unk, eos=eos, V=V, unk_penalty=unk_penalty, temperature=temperature,
+                  step0_all_slots=step0_all_slots)
+        for m in members:                                               # every member's limits before anything is allocated
+            mem = _Member(m[0], m[1], m[2], m[3], sh)
+            self.ok = mem.ok
+            if not self.ok:
+                return
+            self.members.append(mem)
+        keep = self._keep = []
+        # state: one int32 and one float32 block, so that the read-back at the end is two copies
+        M2 = max_len + 2
+        isz = dict(tok_hist=M2 * N, par_hist=M2 * N, fin_step=B * beam, fin_row=B * beam, nfin=B, finished=B, steps=B, blacklist=N,
+                   anc=N * (max_len + 1), cand_idx=N * 2 * beam)
+        fsz = dict(cum_hist=M2 * N, fin_score=B * beam, cand_val=N * 2 * beam)
+        self.ibuf = torch.empty((sum(isz.values()),), dtype=torch.int32, device=dev)
+        self.fbuf = torch.empty((sum(fsz.values()),), dtype=torch.float32, device=dev)
+        self.ioff, self.foff = {}, {}
+        o = 0
+        for k, n in isz.items():
+            self.ioff[k] = (o, n); o += n
+        o = 0
+        for k, n in fsz.items():
+            self.foff[k] = (o, n); o += n
+        self.read_i = self.ioff["steps"][0]               # [tok_hist | par_hist | fin_step | fin_row | nfin | finished] come first
+        self.read_f = self.foff["cand_val"][0]
+        if init_scores is not None:
+            init_scores = init_scores.to(device=dev, dtype=torch.float32).contiguous().view(-1)
+            assert init_scores.numel() == N
+            keep.append(init_scores)
+        for mem in self.members:
+            d = mem.desc
+            for k, (o, n) in self.ioff.items():
+                setattr(d, k, self.ibuf.data_ptr() + 4 * o)
+            for k, (o, n) in self.foff.items():
+                setattr(d, k, self.fbuf.data_ptr() + 4 * o)
+            if init_scores is not None:
+                d.init_scores = init_scores.data_ptr()
+        if prefix_tokens is not None and prefix_tokens.numel() == 0:
+            prefix_tokens = None
+        if ngram or prefix_tokens is not None:
+            r = self.rules = L.DecodeRules()
+            r.no_repeat_ngram = ngram
+            if prefix_tokens is not None:
+                assert prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == B
+                self.prefix = prefix_tokens.to(device=dev, dtype=torch.int32).contiguous()
+                keep.append(self.prefix)
+                r.prefix_len, r.prefix = self.prefix.shape[1], self.prefix.data_ptr()
+            self.rules_addr = ctypes.addressof(r)
+        for mem in self.members:
+            mem.fill()
+        self.bufs_of = [mem.bufs for mem in self.members]
+        n = len(self.members)
+        self.desc_array = (ctypes.c_void_p * n)(*[mem.addr for mem in self.members])     # the HOST array of descriptors of the *_ensemble calls
+        self.descs_addr = ctypes.addressof(self.desc_array)
+        # every member's chain up to its logits, then the shared row and sentence launches
+        self.launches_per_step = sum(3 * mem.desc.layers + 2 for mem in self.members) + 2
         self.steps_run = 0
 
     def view_i(self, name):
@@ -165,13 +216,21 @@ class BeamDecodeSession:
         """the whole search; returns the number of steps launched"""
         lib = L.load()
         st = L.stream()
-        L.check(lib.s2t_decode_begin(self.addr, int(bos), st), "s2t_decode_begin")
+        n = len(self.members)
+        one = self.members[0].addr if n == 1 else None      # one model: the one-model entry points, as ever
+        if one:
+            L.check(lib.s2t_decode_begin(one, int(bos), st), "s2t_decode_begin")
+        else:
+            L.check(lib.s2t_decode_begin_ensemble(self.descs_addr, n, int(bos), st), "s2t_decode_begin_ensemble")
         exec_ = ctypes.c_void_p(0)
         per = POLL_STEPS if graph else 1                    # steps per launch: one recorded graph holds POLL_STEPS of them
-        if graph and self.rules_addr:
-            L.check(lib.s2t_decode_graph_create_rules(self.addr, self.rules_addr, per, ctypes.addressof(exec_)), "s2t_decode_graph_create_rules")
+        if graph and not one:
+            L.check(lib.s2t_decode_graph_create_ensemble(self.descs_addr, n, self.rules_addr, per, ctypes.addressof(exec_)),
+                    "s2t_decode_graph_create_ensemble")
+        elif graph and self.rules_addr:
+            L.check(lib.s2t_decode_graph_create_rules(one, self.rules_addr, per, ctypes.addressof(exec_)), "s2t_decode_graph_create_rules")
         elif graph:
-            L.check(lib.s2t_decode_graph_create(self.addr, per, ctypes.addressof(exec_)), "s2t_decode_graph_create")
+            L.check(lib.s2t_decode_graph_create(one, per, ctypes.addressof(exec_)), "s2t_decode_graph_create")
         fo, fn = self.ioff["finished"]
         finished = self.ibuf[fo:fo + fn]
         steps = 0
@@ -179,10 +238,12 @@ class BeamDecodeSession:
             while steps < self.max_len + 1:
                 if graph:
                     L.check(lib.s2t_decode_graph_launch(exec_.value, st), "s2t_decode_graph_launch")
+                elif not one:
+                    L.check(lib.s2t_decode_step_ensemble(self.descs_addr, n, self.rules_addr, st), "s2t_decode_step_ensemble")
                 elif self.rules_addr:
-                    L.check(lib.s2t_decode_step_rules(self.addr, self.rules_addr, st), "s2t_decode_step_rules")
+                    L.check(lib.s2t_decode_step_rules(one, self.rules_addr, st), "s2t_decode_step_rules")
                 else:
-                    L.check(lib.s2t_decode_step(self.addr, st), "s2t_decode_step")
+                    L.check(lib.s2t_decode_step(one, st), "s2t_decode_step")
                 steps += per                                # (the last graph may run past max_len: its kernels return at once there)
                 if steps % POLL_STEPS == 0 and steps < self.max_len + 1 and bool(finished.all()):
                     break
@@ -215,6 +276,25 @@ class BeamDecodeSession:
             out[int(sent[f])].append({"tokens": tok_d[f, :n], "score": score_d[f], "attention": None, "alignment": None,
                                       "positional_scores": pos_d[f, :n], "origin": int(origin[f]), "_score": float(score[f])})
         return out
+
+
+class BeamDecodeSession(EnsembleDecodeSession):
+    """State + launch sequence of one beam search.  enc_out [Ts, B, D] (one column per SENTENCE), enc_klen int32 [B] or None.
+    no_repeat_ngram_size: 0 (off) or >= 2 (1 is refused: `ok` False); prefix_tokens: integer [B, P], pad = free, WITHOUT EOS (the
+    caller checks: sequence_generator._device_search) -- the session keeps its int32 device copy alive for the recorded graph.
+    The one-member form of EnsembleDecodeSession: `desc`, `addr` and `bufs` are the member's, and `run` goes through the one-model
+    entry points (s2t_decode_begin, s2t_decode_step[_rules], s2t_decode_graph_create[_rules])."""
+
+    def __init__(self, engine, pfx, enc_out, enc_klen, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0,
+                 init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None):
+        super().__init__([(engine, pfx, enc_out, enc_klen)], beam, max_len, min_len, pad, unk, eos, V, unk_penalty, temperature,
+                         init_scores=init_scores, step0_all_slots=step0_all_slots, no_repeat_ngram_size=no_repeat_ngram_size,
+                         prefix_tokens=prefix_tokens)
+        if self.members:
+            m = self.members[0]
+            self.desc, self.addr, self.layers = m.desc, m.addr, m.layers
+        if self.ok:
+            self.bufs = self.members[0].bufs
 
 
 def walk_records(tok_h, par_h, cum_h, nfin, fin_step, fin_row, fin_score, beam, pad, eos, normalize_scores, len_penalty):

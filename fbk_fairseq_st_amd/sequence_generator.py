@@ -14,9 +14,10 @@ in-place K/V rows, output projection, log-softmax) is a libs2t_hip.so kernel; to
 integer selection bookkeeping (top-k, gathers of token/score rows) exactly as the reference does.
 Ensembles (EnsembleModel.forward_decoder :711-770: every member runs its own encoder and incremental decoder, the
 log-probabilities meet in one logsumexp kernel), prefix tokens (:270-280,449-476) and n-gram blocking (:617-650) follow the
-reference.  One model's search runs device-resident (decode.py), n-gram blocking with n >= 2 and prefix tokens without EOS included: both
-are score rules of its per-row kernel.  The step-by-step loop below serves ensembles, `retain_attention`, `--layernorm-embedding`,
-n-gram size 1 and a prefix that holds EOS (and S2T_DEVICE_SEARCH=0); with `retain_attention=True` every hypothesis carries its `attention` (src_len x tgt_len, the last decoder layer's
+reference.  The search of one model or of an ensemble of up to eight runs device-resident (decode.py), n-gram blocking with n >= 2 and prefix
+tokens without EOS included: both are score rules of its per-row kernel, which for an ensemble also takes the log of the members' mean
+probability.  The step-by-step loop below serves `retain_attention`, `--layernorm-embedding`, n-gram size 1, a prefix that holds EOS,
+ensembles whose members differ in compute dtype or hold a member outside the device route's shape limits (and S2T_DEVICE_SEARCH=0); with `retain_attention=True` every hypothesis carries its `attention` (src_len x tgt_len, the last decoder layer's
 encoder-attention averaged over heads and ensemble members: sequence_generator.py:286-292,510-560,757-768) and, with `print_alignment`, the
 hard `alignment` generate.py prints (utils.extract_hard_alignment, fairseq/utils.py); sampling is not part of this path.  `TwoPhaseSequenceGenerator` runs the same loop twice for dual-decoder
 models: transcripts with the auxiliary decoder, then translations seeded by the transcript scores.
@@ -142,31 +143,40 @@ class SequenceGenerator:
         order0 = torch.arange(B, device=enc.encoder_out.device).repeat_interleave(self.beam_size)
         return decoder.owner.encoder.reorder_encoder_out(enc, order0)
 
-    def _device_search(self, decoder, enc, B, max_len, search, bos_token, pad, unk, eos, V, prev_scores, prefix_tokens=None):
-        """The whole loop inside libs2t_hip.so (decode.py / csrc/decode.hip) for the plain or the hierarchical beam search of one model,
-        with n-gram blocking and prefix tokens as score rules of its per-row launch; None when this search needs the step-by-step path
-        below: n-gram size 1 (the reference then bans EOS through the <bos> column), a prefix that holds EOS (the reference then copies
-        slot 0 over the sentence's other slots, :449-476), or a shape the session refuses."""
+    def _device_search(self, decoders, encs, B, max_len, search, bos_token, pad, unk, eos, V, prev_scores, prefix_tokens=None):
+        """The whole loop inside libs2t_hip.so (decode.py / csrc/decode.hip) for the plain or the hierarchical beam search of one model
+        or of an ensemble of up to eight (every member's launches up to its logits, then one row launch that takes the log of the
+        members' mean probability), with n-gram blocking and prefix tokens as score rules of the per-row launch; None when this search
+        needs the step-by-step path below: n-gram size 1 (the reference then bans EOS through the <bos> column), a prefix that holds
+        EOS (the reference then copies slot 0 over the sentence's other slots, :449-476), members of different compute dtypes, or a
+        shape the session refuses for any member."""
         from . import decode as DEC
         if not DEC.device_search_enabled() or type(search) not in (BeamSearch, HierarchicalBeamSearch):
             return None
         ngram = max(self.no_repeat_ngram_size, 0)
         if ngram == 1:
             return None
-        eng = decoder.engine
-        if eng.hp.layernorm_embedding:                                     # the step's first launch takes the embedding sum as it is
+        engs = [d.engine for d in decoders]
+        if any(e.hp.layernorm_embedding for e in engs):                    # the step's first launch takes the embedding sum as it is
             return None
-        eo = enc.encoder_out.contiguous()
-        if not eo.is_cuda:       # host tensors only reach this class under the CPU tests' stand-in engine (tests/cpu_stubs.py: host logic)
+        eos_ = [e.encoder_out.contiguous() for e in encs]
+        if not all(eo.is_cuda for eo in eos_):   # host tensors only reach this class under the CPU tests' stand-in engine (tests/cpu_stubs.py: host logic)
+            return None
+        if any(e.dtype != engs[0].dtype for e in engs):                    # one search state, one row launch: one compute dtype
             return None
         if prefix_tokens is not None:
-            prefix_tokens = prefix_tokens.to(eo.device)
+            prefix_tokens = prefix_tokens.to(eos_[0].device)
             if bool(prefix_tokens.eq(eos).any()):                          # one host sync per search
                 return None
-        klen = enc.src_lengths.to(torch.int32) if enc.encoder_padding_mask is not None else None
-        ses = DEC.BeamDecodeSession(eng, decoder.pfx, eo, klen, self.beam_size, max_len, self.min_len, pad, unk, eos, V, self.unk_penalty,
-                                    self.temperature, init_scores=prev_scores, step0_all_slots=prev_scores is not None,
-                                    no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens)
+        klens = [e.src_lengths.to(torch.int32) if e.encoder_padding_mask is not None else None for e in encs]
+        if len(decoders) == 1:
+            ses = DEC.BeamDecodeSession(engs[0], decoders[0].pfx, eos_[0], klens[0], self.beam_size, max_len, self.min_len, pad, unk, eos, V,
+                                        self.unk_penalty, self.temperature, init_scores=prev_scores, step0_all_slots=prev_scores is not None,
+                                        no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens)
+        else:
+            ses = DEC.EnsembleDecodeSession([(g, d.pfx, eo, kl) for g, d, eo, kl in zip(engs, decoders, eos_, klens)], self.beam_size, max_len,
+                                            self.min_len, pad, unk, eos, V, self.unk_penalty, self.temperature, init_scores=prev_scores,
+                                            step0_all_slots=prev_scores is not None, no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens)
         if not ses.ok:
             return None
         self.last_stats["steps"] = ses.run(eos if bos_token is None else bos_token, graph=self.device_graph)
@@ -188,8 +198,8 @@ class SequenceGenerator:
         beam = self.beam_size
         decoders = list(decoder) if isinstance(decoder, (list, tuple)) else [decoder]
         encs = list(enc) if isinstance(decoder, (list, tuple)) else [enc]
-        if len(decoders) == 1 and not self.retain_attention and decoders[0].owner.training is False:
-            out = self._device_search(decoders[0], encs[0], B, max_len, search, bos_token, pad, unk, eos, V, prev_scores, prefix_tokens)
+        if 1 <= len(decoders) <= 8 and not self.retain_attention and all(d.owner.training is False for d in decoders):
+            out = self._device_search(decoders, encs, B, max_len, search, bos_token, pad, unk, eos, V, prev_scores, prefix_tokens)
             if out is not None:
                 return out
         encs = [self._expand(d, e, B) for d, e in zip(decoders, encs)]

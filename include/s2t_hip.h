@@ -422,7 +422,12 @@ int s2t_scale_by_device_scalar(int dtype, void* x, size_t n, const float* scalar
  * The *_rules calls add, in the per-row launch and in the reference's order after the rules above, prefix tokens
  * (sequence_generator.py:270-280,449-476) and n-gram blocking (:596-650); their limits: n-gram size 0 (off) or >= 2 -- with 1 the reference
  * bans EOS through the <bos> column and the search never finalises (S2T_ENOTSUP); a prefix without EOS -- the reference then copies slot 0
- * over the sentence's other slots, which this path does not do (the CALLER checks: the tokens are device memory).  One model only. */
+ * over the sentence's other slots, which this path does not do (the CALLER checks: the tokens are device memory).
+ * The *_ensemble calls run the search over 2..8 models at once (fairseq/sequence_generator.py:757-768 EnsembleModel.forward_decoder): one
+ * descriptor per member, all of them naming ONE search state.  A step is every member's 3 * layers_j + 2 launches up to its logits, one
+ * member after the other, then one row launch that takes the log of the members' mean probability (each member's log-softmax as above,
+ * combined per column as s2t_ensemble_lse does: m = max_j lp_j; -inf if m is; else m + log(sum_j exp(lp_j - m)) - log n) before the
+ * rules, and one sentence launch that also embeds the chosen tokens for every member: sum_j (3 * layers_j + 2) + 2 launches. */
 typedef struct S2TDecodeLayer {
     const void *ln1_g, *ln1_b;       /* f32 [D]: self_attn_layer_norm */
     /* every w_* below is the nn.Linear weight in FRAGMENT-MAJOR order (s2t_decode_pack_weight): [rows / 16][K / ks][64 lanes][16 bytes] */
@@ -495,6 +500,18 @@ size_t s2t_decode_lds_bytes(const S2TDecodeDesc* d);
 int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec);
 /* the same recording of n_steps x s2t_decode_step_rules(d, r); arguments checked as there (and graph_exec, n_steps first: S2T_EINVAL) */
 int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDecodeRules* r, int n_steps, void** graph_exec);
+/* The same three calls for an ensemble.  d: a HOST array of n HOST descriptors (and their HOST layer arrays), read during the call only.
+ * Members may differ in D, heads, layers, ffn, ffn_slices, Ts, Tsp, enc_klen, embed_scale, ln_eps, gelu and in every weight and buffer
+ * of their own (x0, x1, part0, part1, xn, logits, the layers' caches); they must agree on dtype, B, beam, V, ldv, max_len, min_len, pad,
+ * unk, eos, step0_all_slots, unk_penalty, inv_temperature and on every state pointer (steps, anc, tok_hist, par_hist, cum_hist, blacklist,
+ * nfin, finished, fin_step, fin_row, fin_score, cand_val, cand_idx, init_scores).  Checked before any launch, in this order: d == NULL,
+ * n < 1, n > 8 or a NULL d[j] -> S2T_EINVAL; `r` as s2t_decode_step_rules checks it (begin: no rules); members that disagree on a shared
+ * field -> S2T_EINVAL; every member as s2t_decode_step checks it (S2T_ENOTSUP outside the limits).  graph_create checks graph_exec and
+ * n_steps (1..64) first (S2T_EINVAL) and leaves *graph_exec NULL on every failure.  n == 1 launches exactly what the *_rules calls launch
+ * for d[0].  Every recording is one chain on one stream (the members do not overlap); s2t_decode_graph_launch / _destroy serve it. */
+int s2t_decode_begin_ensemble(const S2TDecodeDesc* const* d, int n, int bos, void* stream);
+int s2t_decode_step_ensemble(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, void* stream);
+int s2t_decode_graph_create_ensemble(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, int n_steps, void** graph_exec);
 int s2t_decode_graph_launch(void* graph_exec, void* stream);
 int s2t_decode_graph_destroy(void* graph_exec);
 
@@ -528,7 +545,7 @@ int s2t_prof_enable(int on);
  *                  of keeping two in flight; bit-identical results (tools/gemm_deep_check.py); 0 restores the two-set loop;
  *       "ln_small" (default 1): the bf16, D = 512 LayerNorm backward of activations below 8,192 rows requests a wave's rows three at a
  *                  time instead of one ahead (same formulas; results agree with the other kernel to bf16 rounding); 0 restores it;
- *       "decode_stop_after": diagnostic, ends s2t_decode_step after that many launches (0 = off);
+ *       "decode_stop_after": diagnostic, ends s2t_decode_step after that many launches, counted across the members of an ensemble (0 = off);
  * returns the previous value, or S2T_EINVAL (-22) for an unknown key or a value out of range. */
 int s2t_set_option(const char* key, int value);
 int s2t_prof_read(const char* family, double* ms, long long* launches, double* flops, double* bytes);
