@@ -1273,16 +1273,40 @@ struct SentArgs {
 // ENS: the other members' next input (member 0 is SentArgs' own), each from its own embedding, position table, D and scale
 struct SentMember { const void* embed; const float* pos_table; float* x0; int D; float embed_scale; };
 struct SentEnsArgs : SentArgs { int n_more; SentMember more[ENS_MAX - 1]; };
-template <bool ENS> struct SentArgsOf { typedef SentArgs type; };
-template <> struct SentArgsOf<true> { typedef SentEnsArgs type; };
+// DIV (diverse_groups > 1): the groups and the strength ride behind the arguments of the plain forms, whose layout stays as it is
+struct SentDivArgs : SentArgs { int div_groups; float div_strength; };
+struct SentEnsDivArgs : SentEnsArgs { int div_groups; float div_strength; };
+template <bool ENS, bool DIV = false> struct SentArgsOf { typedef SentArgs type; };
+template <> struct SentArgsOf<true, false> { typedef SentEnsArgs type; };
+template <> struct SentArgsOf<false, true> { typedef SentDivArgs type; };
+template <> struct SentArgsOf<true, true> { typedef SentEnsDivArgs type; };
+// an entry's value under the Hamming penalty of group-diverse beam search: v - strength * count, the product and the difference each
+// rounded to f32 (tests/decode_diverse_ref.py restates it bit for bit); -inf stays -inf.  The empty asm keeps the product a value of
+// its own: the device build contracts a * b - c into one fused multiply-add otherwise, through __fmul_rn / __fsub_rn and the fp
+// contract pragma alike (seen in the ISA as v_pk_fma_f32).
+__device__ __forceinline__ float div_penalised(float v, float strength, int count) {
+    float pen = __fmul_rn(strength, (float)count);
+    asm volatile("" : "+v"(pen));
+    return __fsub_rn(v, pen);
+}
 __device__ __forceinline__ int ens_more(const SentArgs&) { return 0; }
 __device__ __forceinline__ int ens_more(const SentEnsArgs& a) { return a.n_more; }
 __device__ __forceinline__ SentMember ens_member(const SentArgs& a, int) { return SentMember{a.embed, a.pos_table, a.x0, a.D, a.embed_scale}; }
 __device__ __forceinline__ SentMember ens_member(const SentEnsArgs& a, int j) {
     return j == 0 ? SentMember{a.embed, a.pos_table, a.x0, a.D, a.embed_scale} : a.more[j - 1];
 }
-template <typename T, bool ENS = false>
-__global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<ENS>::type a) {
+// DIV: group-diverse beam search (fairseq/search.py:103-161, Vijayakumar et al.) with G = div_groups > 1 groups of mg = beam / G slots and a
+// strength >= 0.  Only the forming of the 2 beam ranked candidates differs: group g owns the slots g, g + G, ... (at step 0 slot g alone:
+// every slot is the same there, and the lists are those of the sentence's first row, the only one the row launch fills), its entries are
+// the 2 beam list entries of its rows, each lowered by strength x (how many of the candidates the groups before it took at this step
+// have the entry's token -- all 2 mg of a group, as the reference's scatter_add_ counts them), and it takes its 2 mg best (value
+// descending, then (row's index within the group) V + column ascending); its j-th becomes candidate j G + g, as the reference
+// interleaves them.  The penalties only lower values and group g meets at most 2 mg g distinct penalised tokens, so a row's 2 mg best
+// penalised entries lie among its 2 beam best unpenalised ones: the lists the row launch writes are enough, for any strength >= 0.
+// One wave: a lane holds up to four of the group's <= 8 x 32 entries; the taken tokens are read from the lanes that keep them (rank =
+// lane) by scalar broadcasts; 2 mg arg-max rounds per group, 2 beam in all as in the merge.
+template <typename T, bool ENS = false, bool DIV = false>
+__global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<ENS, DIV>::type a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ __attribute__((aligned(16))) float l_val[16 * 32];
     __shared__ __attribute__((aligned(16))) int l_idx[16 * 32];
@@ -1322,7 +1346,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int i = tid + u * NTHREADS;
-        if (i < ne) { l_val[i] = ev[u]; l_idx[i] = (i / K2) * a.V + ei[u]; }      // flat index: row * V + column
+        if (i < ne) { l_val[i] = ev[u]; l_idx[i] = DIV ? ei[u] : (i / K2) * a.V + ei[u]; }      // flat index: row * V + column (DIV: the column)
     }
     __syncthreads();
     DSTAMP(4, 1);
@@ -1330,15 +1354,50 @@ __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<
         // k-way merge of the `rows` sorted lists: lane j < rows offers the head of list j; the winner of round r becomes candidate r,
         // kept by lane r.  (Measured alternatives for 50 entries against the 5,900 cycles of these k = 10 rounds: every entry counting
         // the entries before it over the lists in LDS 10,700; the same count through scalar broadcasts of one entry per lane 11,300.)
-        int head = 0;
+        [[maybe_unused]] int head = 0;                             // (declared here, before my_val, as ever: the plain forms' registers stay put)
         float my_val = -INFINITY; int my_tok = 0, my_row = n0;
-        for (int r = 0; r < k; ++r) {
-            float v = -INFINITY; int flat = 0x7fffffff;
-            if (tid < rows && head < K2) { v = l_val[tid * K2 + head]; flat = l_idx[tid * K2 + head]; }
-            float mv; int mf;
-            wave_argmax(v, flat, mv, mf);
-            if (flat == mf && tid < rows) ++head;
-            if (tid == r) { my_val = mv; my_tok = mf % a.V; my_row = n0 + mf / a.V; }
+        if constexpr (DIV) {
+            const int G = a.div_groups, mg = beam / G, kg = 2 * mg;        // k == K2 == G * kg (V >= 2 beam + 1: desc_ok)
+            const int ne_g = (first ? 1 : mg) * K2;                        // a group's entries: <= 8 rows x 32 = 4 per lane
+            for (int g = 0; g < G; ++g) {
+                float pv[4]; int key[4], col[4], cnt[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int e = min(tid + 64 * u, ne_g - 1), i = e / K2;
+                    const int src = (first ? 0 : g + i * G) * K2 + (e - i * K2);
+                    pv[u] = l_val[src]; col[u] = l_idx[src]; cnt[u] = 0;
+                    key[u] = tid + 64 * u < ne_g ? i * a.V + col[u] : 0x7fffffff;
+                }
+                for (int j = 0; j < kg; ++j)
+                    for (int gp = 0; gp < g; ++gp) {
+                        const int taken = __builtin_amdgcn_readlane(my_tok, j * G + gp);
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) cnt[u] += col[u] == taken ? 1 : 0;
+                    }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) pv[u] = key[u] != 0x7fffffff ? div_penalised(pv[u], a.div_strength, cnt[u]) : -INFINITY;
+                for (int j = 0; j < kg; ++j) {
+                    float bv = -INFINITY; int bk = 0x7fffffff;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (key[u] != 0x7fffffff && cand_better(pv[u], key[u], bv, bk)) { bv = pv[u]; bk = key[u]; }
+                    float mv; int mk;
+                    wave_argmax(bv, bk, mv, mk);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (key[u] == mk) { key[u] = 0x7fffffff; pv[u] = -INFINITY; }       // taken (keys are unique; ne_g >= kg entries)
+                    if (tid == j * G + g) { my_val = mv; my_tok = mk % a.V; my_row = n0 + (first ? g : g + (mk / a.V) * G); }
+                }
+            }
+        } else {
+            for (int r = 0; r < k; ++r) {
+                float v = -INFINITY; int flat = 0x7fffffff;
+                if (tid < rows && head < K2) { v = l_val[tid * K2 + head]; flat = l_idx[tid * K2 + head]; }
+                float mv; int mf;
+                wave_argmax(v, flat, mv, mf);
+                if (flat == mf && tid < rows) ++head;
+                if (tid == r) { my_val = mv; my_tok = mf % a.V; my_row = n0 + mf / a.V; }
+            }
         }
         DSTAMP(4, 2);
         const int nb = min(beam, k);
@@ -1521,6 +1580,7 @@ template <typename T> hipError_t configure() {
         if ((e = configure_dd<T, 512>()) != hipSuccess) return e;
     }
     DEC_ALLOW(dec_sent_kernel<T>); DEC_ALLOW((dec_sent_kernel<T, true>));
+    DEC_ALLOW((dec_sent_kernel<T, false, true>)); DEC_ALLOW((dec_sent_kernel<T, true, true>));
     DEC_ALLOW((dec_logits_kernel<T, 1>)); DEC_ALLOW((dec_logits_kernel<T, 2>)); DEC_ALLOW((dec_logits_kernel<T, 3>)); DEC_ALLOW((dec_logits_kernel<T, 4>));
     DEC_ALLOW((dec_logits_kernel<T, 5>)); DEC_ALLOW((dec_logits_kernel<T, 6>)); DEC_ALLOW((dec_logits_kernel<T, 7>)); DEC_ALLOW((dec_logits_kernel<T, 8>));
     return hipSuccess;
@@ -1661,9 +1721,11 @@ int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
 #undef DEC_ROW
     }
     {
-        SentArgs a;
+        SentDivArgs a;
         sent_args(d, a);
-        hipLaunchKernelGGL(dec_sent_kernel<T>, dim3(B), dim3(NTHREADS), need.sent, st, a);
+        a.div_groups = d->diverse_groups; a.div_strength = d->diverse_strength;
+        if (d->diverse_groups > 1) hipLaunchKernelGGL((dec_sent_kernel<T, false, true>), dim3(B), dim3(NTHREADS), need.sent, st, a);
+        else hipLaunchKernelGGL(dec_sent_kernel<T>, dim3(B), dim3(NTHREADS), need.sent, st, static_cast<const SentArgs&>(a));
     }
     S2T_LAUNCH_CHECK();
     return S2T_OK;
@@ -1692,15 +1754,17 @@ int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r
 #undef DEC_ROW
     }
     {
-        SentEnsArgs a;
+        SentEnsDivArgs a;
         sent_args(d, a);
+        a.div_groups = d->diverse_groups; a.div_strength = d->diverse_strength;
         a.n_more = n - 1;
         for (int j = 1; j < ENS_MAX; ++j) {
             SentMember& o = a.more[j - 1];
             if (j < n) { o.embed = dv[j]->embed; o.pos_table = dv[j]->pos_table; o.x0 = dv[j]->x0; o.D = dv[j]->D; o.embed_scale = dv[j]->embed_scale; }
             else { o.embed = nullptr; o.pos_table = nullptr; o.x0 = nullptr; o.D = 0; o.embed_scale = 0.f; }
         }
-        hipLaunchKernelGGL((dec_sent_kernel<T, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, a);
+        if (d->diverse_groups > 1) hipLaunchKernelGGL((dec_sent_kernel<T, true, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, a);
+        else hipLaunchKernelGGL((dec_sent_kernel<T, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, static_cast<const SentEnsArgs&>(a));
     }
     S2T_LAUNCH_CHECK();
     return S2T_OK;
@@ -1732,8 +1796,19 @@ extern "C" size_t s2t_decode_lds_bytes(const S2TDecodeDesc* d) {
     return m > n.sent ? m : n.sent;
 }
 
+// group-diverse beam search (diverse_groups > 1), in the order include/s2t_hip.h documents; 0 or 1 is the plain search
+static int diverse_check(const S2TDecodeDesc* d) {
+    if (d->diverse_groups < 0) return S2T_EINVAL;
+    if (d->diverse_groups <= 1) return S2T_OK;
+    if (d->beam % d->diverse_groups != 0) return S2T_EINVAL;
+    if (!(d->diverse_strength >= 0.f) || !std::isfinite(d->diverse_strength)) return S2T_ENOTSUP;     // a reward breaks the top-2*beam argument
+    if (d->step0_all_slots) return S2T_ENOTSUP;
+    return S2T_OK;
+}
 static int decode_check(const S2TDecodeDesc* d) {
     if (!d) return S2T_EINVAL;
+    const int dc = diverse_check(d);
+    if (dc != S2T_OK) return dc;
     if (!desc_ok(d)) return S2T_ENOTSUP;
     if (s2t_decode_lds_bytes(d) > LDS_CAP) return S2T_ENOTSUP;
     if (!d->x0 || !d->x1 || !d->part0 || !d->part1 || !d->xn || !d->logits || !d->steps || !d->anc || !d->cand_val || !d->cand_idx ||
@@ -1785,7 +1860,8 @@ static int ensemble_check(const S2TDecodeDesc* const* dv, int n, const S2TDecode
         const S2TDecodeDesc* b = dv[j];
         if (a->dtype != b->dtype || a->B != b->B || a->beam != b->beam || a->V != b->V || a->ldv != b->ldv || a->max_len != b->max_len ||
             a->min_len != b->min_len || a->pad != b->pad || a->unk != b->unk || a->eos != b->eos || a->step0_all_slots != b->step0_all_slots ||
-            a->unk_penalty != b->unk_penalty || a->inv_temperature != b->inv_temperature)
+            a->unk_penalty != b->unk_penalty || a->inv_temperature != b->inv_temperature || a->diverse_groups != b->diverse_groups ||
+            a->diverse_strength != b->diverse_strength)
             return S2T_EINVAL;
         if (a->steps != b->steps || a->anc != b->anc || a->tok_hist != b->tok_hist || a->par_hist != b->par_hist || a->cum_hist != b->cum_hist ||
             a->blacklist != b->blacklist || a->nfin != b->nfin || a->finished != b->finished || a->fin_step != b->fin_step ||

@@ -12,12 +12,13 @@ logits into its own buffers, one member after the other, then one row launch tak
 score rules and one sentence launch does the bookkeeping and embeds the chosen tokens for every member:
 `sum_j (3 * layers_j + 2) + 2` launches per step.  The members may differ in width, depth and encoder length.
 
-`SequenceGenerator` (sequence_generator.py) takes this path for one model or an ensemble with the plain or the hierarchical beam
-search, with n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch
+`SequenceGenerator` (sequence_generator.py) takes this path for one model or an ensemble with the plain, the hierarchical or the
+group-diverse beam search (`diverse_groups`: the per-sentence launch forms the groups' penalised candidates from the same row lists), with n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch
 (`s2t_decode_step_rules`), and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for attention output,
 a prefix that holds EOS, n-gram size 1, members of different dtypes and any member outside the shape limits.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -62,6 +63,7 @@ class _Member:
         d.pad, d.unk, d.eos, d.step0_all_slots = sh["pad"], sh["unk"], sh["eos"], int(bool(sh["step0_all_slots"]))
         d.ln_eps, d.embed_scale = hp.ln_eps, 1.0 if hp.no_scale_embedding else float(D) ** 0.5
         d.unk_penalty, d.inv_temperature = float(sh["unk_penalty"]), 1.0 / float(sh["temperature"])
+        d.diverse_groups, d.diverse_strength = int(sh.get("diverse_groups", 0)), float(sh.get("diverse_strength", 0.0))
         self.layers = (L.DecodeLayer * hp.dec_layers)()
         d.layer = ctypes.addressof(self.layers)
         self.addr = ctypes.addressof(d)
@@ -128,10 +130,12 @@ class EnsembleDecodeSession:
     SENTENCE), enc_klen int32 [B] or None; the members may differ in everything of their own (width, depth, encoder length) and must
     have one compute dtype.  The search state (records, candidates, ancestor table, step counters) exists ONCE and every member's
     descriptor names it; `members[j].bufs` / `bufs_of[j]` are member j's own buffers.  `ok` False: a member, the rules or the
-    combination is refused and nothing ran.  The other arguments as BeamDecodeSession's."""
+    combination is refused and nothing ran.  diverse_groups G > 1: group-diverse beam search (fairseq/search.py:103-161) with
+    diverse_strength >= 0, a form of the per-sentence launch (G must divide the beam; not with step0_all_slots); 0 or 1: plain.
+    The other arguments as BeamDecodeSession's."""
 
     def __init__(self, members, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0, init_scores=None,
-                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None):
+                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0, diverse_strength=0.5):
         members = list(members)
         assert members, "an ensemble needs at least one member"
         engine, enc_out = members[0][0], members[0][2]
@@ -144,10 +148,13 @@ class EnsembleDecodeSession:
         self.rules, self.rules_addr = None, None                        # S2TDecodeRules when a rule beyond the descriptor's is set
         self.members = []
         self.ok = ngram != 1 and 1 <= len(members) <= 8 and all(m[0].dtype == engine.dtype and m[2].shape[1] == B for m in members)
+        G, lam = int(diverse_groups), float(diverse_strength)
+        if G < 0 or (G > 1 and (beam % G != 0 or not (lam >= 0.0 and math.isfinite(lam)) or step0_all_slots)):
+            self.ok = False                                             # what the C ABI refuses (include/s2t_hip.h: diverse_groups)
         if not self.ok:
             return
         sh = dict(beam=beam, max_len=max_len, min_len=min_len, pad=pad, unk=unk, eos=eos, V=V, unk_penalty=unk_penalty, temperature=temperature,
-                  step0_all_slots=step0_all_slots)
+                  step0_all_slots=step0_all_slots, diverse_groups=G, diverse_strength=lam)
         for m in members:                                               # every member's limits before anything is allocated
             mem = _Member(m[0], m[1], m[2], m[3], sh)
             self.ok = mem.ok
@@ -286,10 +293,11 @@ class BeamDecodeSession(EnsembleDecodeSession):
     entry points (s2t_decode_begin, s2t_decode_step[_rules], s2t_decode_graph_create[_rules])."""
 
     def __init__(self, engine, pfx, enc_out, enc_klen, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0,
-                 init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None):
+                 init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0,
+                 diverse_strength=0.5):
         super().__init__([(engine, pfx, enc_out, enc_klen)], beam, max_len, min_len, pad, unk, eos, V, unk_penalty, temperature,
                          init_scores=init_scores, step0_all_slots=step0_all_slots, no_repeat_ngram_size=no_repeat_ngram_size,
-                         prefix_tokens=prefix_tokens)
+                         prefix_tokens=prefix_tokens, diverse_groups=diverse_groups, diverse_strength=diverse_strength)
         if self.members:
             m = self.members[0]
             self.desc, self.addr, self.layers = m.desc, m.addr, m.layers

@@ -153,14 +153,16 @@ class DecodeLayer(ctypes.Structure):
 
 
 class DecodeDesc(ctypes.Structure):
-    """S2TDecodeDesc of include/s2t_hip.h"""
+    """S2TDecodeDesc of include/s2t_hip.h (diverse_groups / diverse_strength were appended behind the fields of ABI version 9, which the
+    library still reports: zero in both is the plain search)"""
     _fields_ = ([(n, c_int) for n in ("dtype", "B", "beam", "D", "heads", "ffn", "layers", "V", "ldv", "Ts", "Tsp", "max_len", "min_len",
                                       "ffn_slices", "gelu", "pad", "unk", "eos", "step0_all_slots")] +
                 [(n, c_float) for n in ("ln_eps", "embed_scale", "unk_penalty", "inv_temperature")] +
                 [(n, c_void_p) for n in ("layer", "lnf_g", "lnf_b", "w_out", "embed", "pos_table", "enc_klen", "init_scores",
                                          "x0", "x1", "part0", "part1", "xn", "logits", "steps", "anc", "cand_val", "cand_idx",
                                          "tok_hist", "par_hist", "cum_hist", "blacklist", "nfin", "finished", "fin_step", "fin_row",
-                                         "fin_score")])
+                                         "fin_score")] +
+                [("diverse_groups", c_int), ("diverse_strength", c_float)])
 
 
 class DecodeRules(ctypes.Structure):

@@ -347,19 +347,30 @@ class FairseqTask(_TaskBase):
         return loss, sample_size, logging_output
 
     def build_generator(self, models, args):
-        """fairseq_task.py:230-313 (beam search only: sampling / diverse search / scoring are outside the S2T path)."""
-        from .sequence_generator import SequenceGenerator
+        """fairseq_task.py:230-313: beam search, or group-diverse beam search with --diverse-beam-groups / --diverse-beam-strength
+        (sampling, scoring and the length-constrained search are outside the S2T path)."""
+        from .sequence_generator import DiverseBeamSearch, SequenceGenerator
+        sampling, match_source_len = getattr(args, "sampling", False), getattr(args, "match_source_len", False)
+        groups, rate = getattr(args, "diverse_beam_groups", -1), getattr(args, "diversity_rate", -1)
+        if sum(int(bool(c)) for c in (sampling, groups > 0, match_source_len, rate > 0)) > 1:       # fairseq_task.py:252-264
+            raise ValueError("Provided Search parameters are mutually exclusive.")
         for flag in ("score_reference", "sampling", "match_source_len"):
             if getattr(args, flag, False):
                 raise NotImplementedError("--%s is outside the S2T hot path" % flag.replace("_", "-"))
-        if getattr(args, "diverse_beam_groups", -1) > 0 or getattr(args, "diversity_rate", -1) > 0:
-            raise NotImplementedError("diverse beam search is outside the S2T hot path")
+        if rate > 0:
+            # fairseq/search.py:338 takes the beam of a candidate with torch.div on integers, which is true division in current torch: the
+            # reference's own DiverseSiblingsSearch hands float beam indices to the generator, so there is no behaviour to reproduce
+            raise NotImplementedError("--diversity-rate (DiverseSiblingsSearch) is refused: the reference computes its beam indices with "
+                                      "torch.div on integers (fairseq/search.py:338), which yields floats under current torch")
+        search = None
+        if groups > 0:
+            search = DiverseBeamSearch(self.target_dictionary, groups, getattr(args, "diverse_beam_strength", 0.5))
         return SequenceGenerator(models, self.target_dictionary, beam_size=getattr(args, "beam", 5),
                                  max_len_a=getattr(args, "max_len_a", 0), max_len_b=getattr(args, "max_len_b", 200),
                                  min_len=getattr(args, "min_len", 1), normalize_scores=(not getattr(args, "unnormalized", False)),
                                  len_penalty=getattr(args, "lenpen", 1), unk_penalty=getattr(args, "unkpen", 0),
                                  temperature=getattr(args, "temperature", 1.0),
-                                 no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0),
+                                 no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=search,
                                  print_alignment=getattr(args, "print_alignment", False))     # fairseq_task.py:300-303
 
     def inference_step(self, generator, models, sample, prefix_tokens=None):      # fairseq_task.py:392-394

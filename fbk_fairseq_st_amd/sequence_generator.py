@@ -19,7 +19,10 @@ tokens without EOS included: both are score rules of its per-row kernel, which f
 probability.  The step-by-step loop below serves `retain_attention`, `--layernorm-embedding`, n-gram size 1, a prefix that holds EOS,
 ensembles whose members differ in compute dtype or hold a member outside the device route's shape limits (and S2T_DEVICE_SEARCH=0); with `retain_attention=True` every hypothesis carries its `attention` (src_len x tgt_len, the last decoder layer's
 encoder-attention averaged over heads and ensemble members: sequence_generator.py:286-292,510-560,757-768) and, with `print_alignment`, the
-hard `alignment` generate.py prints (utils.extract_hard_alignment, fairseq/utils.py); sampling is not part of this path.  `TwoPhaseSequenceGenerator` runs the same loop twice for dual-decoder
+hard `alignment` generate.py prints (utils.extract_hard_alignment, fairseq/utils.py); sampling is not part of this path.
+Group-diverse beam search (`DiverseBeamSearch`, --diverse-beam-groups: fairseq/search.py:103-161) runs device-resident too for a
+strength >= 0 -- the groups' penalised selections are made from the rows' 2 * beam best by the per-sentence launch -- and on the
+step-by-step loop for a negative strength.  `TwoPhaseSequenceGenerator` runs the same loop twice for dual-decoder
 models: transcripts with the auxiliary decoder, then translations seeded by the transcript scores.
 """
 import math
@@ -60,6 +63,40 @@ class HierarchicalBeamSearch(BeamSearch):
         k = min(2 * beam, cand.shape[1] - 1)
         top_s, top_i = torch.topk(cand, k)
         return top_s, top_i % V, top_i // V
+
+
+class DiverseBeamSearch:
+    """fairseq/search.py:103-161 (Vijayakumar et al., Hamming diversity): the beam is split into `num_groups` groups, group g holding the
+    slots g, g + G, ...; the groups run BeamSearch.step one after the other, each on log-probabilities lowered by `diversity_strength`
+    times the number of candidates the earlier groups of this step took with that token, and candidate j of group g becomes overall
+    candidate j * G + g.  The device route (decode.py, `diverse_groups`) makes the same selection from the rows' 2 * beam best."""
+
+    def __init__(self, tgt_dict, num_groups, diversity_strength):
+        self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        self.num_groups = int(num_groups)
+        self.diversity_strength = -float(diversity_strength)               # as the reference keeps it: added, times the counts
+        self.beam = BeamSearch(tgt_dict)
+
+    def step(self, step, lprobs, scores):
+        B, beam, V = lprobs.shape
+        G = self.num_groups
+        if beam % G != 0:
+            raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+        diversity = torch.zeros((B, V), dtype=lprobs.dtype, device=lprobs.device)
+        ones = None
+        out_s, out_i, out_b = [], [], []
+        for g in range(G):
+            lp = lprobs[:, g::G, :]
+            sc = scores[:, g::G, :] if step > 0 else None
+            lp = torch.add(lp, diversity.unsqueeze(1), alpha=self.diversity_strength) if g > 0 else lp.contiguous()
+            top_s, top_i, top_b = self.beam.step(step, lp, sc)
+            out_s.append(top_s); out_i.append(top_i); out_b.append(top_b * G + g)
+            if ones is None:
+                ones = torch.ones(top_i.shape, dtype=diversity.dtype, device=diversity.device)
+            diversity.scatter_add_(1, top_i, ones)                         # index bookkeeping: counts of the tokens taken so far
+        k = out_s[0].shape[1]
+        return (torch.stack(out_s, 2).view(B, k * G), torch.stack(out_i, 2).view(B, k * G), torch.stack(out_b, 2).view(B, k * G))
 
 
 class SequenceGenerator:
@@ -144,15 +181,23 @@ class SequenceGenerator:
         return decoder.owner.encoder.reorder_encoder_out(enc, order0)
 
     def _device_search(self, decoders, encs, B, max_len, search, bos_token, pad, unk, eos, V, prev_scores, prefix_tokens=None):
-        """The whole loop inside libs2t_hip.so (decode.py / csrc/decode.hip) for the plain or the hierarchical beam search of one model
-        or of an ensemble of up to eight (every member's launches up to its logits, then one row launch that takes the log of the
+        """The whole loop inside libs2t_hip.so (decode.py / csrc/decode.hip) for the plain, the hierarchical or the group-diverse beam
+        search (strength >= 0; the groups are a form of the per-sentence launch) of one model or of an ensemble of up to eight (every member's launches up to its logits, then one row launch that takes the log of the
         members' mean probability), with n-gram blocking and prefix tokens as score rules of the per-row launch; None when this search
         needs the step-by-step path below: n-gram size 1 (the reference then bans EOS through the <bos> column), a prefix that holds
         EOS (the reference then copies slot 0 over the sentence's other slots, :449-476), members of different compute dtypes, or a
         shape the session refuses for any member."""
         from . import decode as DEC
-        if not DEC.device_search_enabled() or type(search) not in (BeamSearch, HierarchicalBeamSearch):
+        if not DEC.device_search_enabled() or type(search) not in (BeamSearch, HierarchicalBeamSearch, DiverseBeamSearch):
             return None
+        div = {}
+        if type(search) is DiverseBeamSearch:
+            if self.beam_size % search.num_groups != 0:
+                raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+            strength = -search.diversity_strength
+            if not (strength >= 0.0 and math.isfinite(strength)) or prev_scores is not None:
+                return None                                                # a reward breaks the top-2*beam argument of the sentence launch
+            div = dict(diverse_groups=search.num_groups, diverse_strength=strength)
         ngram = max(self.no_repeat_ngram_size, 0)
         if ngram == 1:
             return None
@@ -172,11 +217,12 @@ class SequenceGenerator:
         if len(decoders) == 1:
             ses = DEC.BeamDecodeSession(engs[0], decoders[0].pfx, eos_[0], klens[0], self.beam_size, max_len, self.min_len, pad, unk, eos, V,
                                         self.unk_penalty, self.temperature, init_scores=prev_scores, step0_all_slots=prev_scores is not None,
-                                        no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens)
+                                        no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens, **div)
         else:
             ses = DEC.EnsembleDecodeSession([(g, d.pfx, eo, kl) for g, d, eo, kl in zip(engs, decoders, eos_, klens)], self.beam_size, max_len,
                                             self.min_len, pad, unk, eos, V, self.unk_penalty, self.temperature, init_scores=prev_scores,
-                                            step0_all_slots=prev_scores is not None, no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens)
+                                            step0_all_slots=prev_scores is not None, no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens,
+                                            **div)
         if not ses.ok:
             return None
         self.last_stats["steps"] = ses.run(eos if bos_token is None else bos_token, graph=self.device_graph)
@@ -366,6 +412,9 @@ class TwoPhaseSequenceGenerator(SequenceGenerator):
     `src_len` (:178,213-218).  Every returned hypothesis carries `aux_tokens`, the transcript it descends from (:966-975)."""
 
     def __init__(self, models, src_dict, tgt_dict, **kw):
+        if isinstance(kw.get("search_strategy"), DiverseBeamSearch):
+            raise NotImplementedError("DiverseBeamSearch is not part of the two-phase generator: its second search is the hierarchical "
+                                      "beam search (twophase_sequence_generator.py:17-49)")
         super().__init__(models, tgt_dict, **kw)
         if not hasattr(self.models[0], "auxiliary_decoder"):
             raise TypeError("TwoPhaseSequenceGenerator needs a model with an auxiliary decoder (conv_transformer_dualdecoder)")

@@ -114,6 +114,9 @@ class SpeechTranslationDualDecodingTask(SpeechTranslationCTCTask):
 
     def build_generator(self, models, args):
         from .sequence_generator import TwoPhaseSequenceGenerator
+        if getattr(args, "diverse_beam_groups", -1) > 0:
+            raise NotImplementedError("--diverse-beam-groups is not part of the two-phase generator: its second search is the "
+                                      "hierarchical beam search (twophase_sequence_generator.py:17-49)")
         return TwoPhaseSequenceGenerator(models, self.source_dictionary, self.target_dictionary, beam_size=getattr(args, "beam", 5),
                                          max_len_a=getattr(args, "max_len_a", 0), max_len_b=getattr(args, "max_len_b", 200),
                                          min_len=getattr(args, "min_len", 1), normalize_scores=(not getattr(args, "unnormalized", False)),

@@ -411,7 +411,8 @@ int s2t_scale_by_device_scalar(int dtype, void* x, size_t n, const float* scalar
  *              C: LayerNorm -> q of one head -> attention over the sentence's encoder rows -> share of the output projection
  *              F: LayerNorm -> one slice of fc1 + activation -> that slice's share of fc2        grid (B, ffn_slices)
  *   then       final LayerNorm; output projection over all N rows; per row: log-softmax, score rules, + cumulative score, 2*beam best;
- *              per sentence: merge, finalise EOS candidates, choose the next beam, record it, embed its tokens for the next step.
+ *              per sentence: merge (diverse_groups > 1: the groups' penalised selections instead), finalise EOS candidates, choose the
+ *              next beam, record it, embed its tokens for the next step.
  * The shares (per head / per slice, in the compute type T) are summed in f32, in a fixed order, by the launch that consumes them, together with the residual and the
  * bias: no atomics, results do not depend on scheduling.  The K/V cache is never re-ordered: anc[n][p] names the slot whose row at
  * position p belongs to hypothesis n's history (the index indirection that replaces reorder_incremental_state's index_select copies),
@@ -467,6 +468,16 @@ typedef struct S2TDecodeDesc {
     int* blacklist;                          /* i32 [N] */
     int* nfin; int* finished;                /* i32 [B] */
     int* fin_step; int* fin_row; float* fin_score;   /* [B][beam]: finalised hypotheses in the order the reference appends them */
+    /* group-diverse beam search (fairseq/search.py:103-161), appended behind the fields above: a zero-initialised descriptor is the plain
+     * search.  diverse_groups G: 0 or 1 = plain (exactly the launches of before); G > 1: the beam is G groups of beam / G slots, group g
+     * the slots g, g + G, ...; the groups choose in order, each from its rows' candidates lowered by diverse_strength x (the number of
+     * candidates the earlier groups of this step took with that token), and candidate j of group g is overall candidate j G + g.  A form
+     * of the per-sentence launch: the number of launches does not change.  Checked by every s2t_decode_* call that takes a descriptor,
+     * first of the descriptor's checks (after d == NULL and the rules) and before any launch, in this order: diverse_groups < 0 ->
+     * S2T_EINVAL; G > 1 and beam % G != 0 -> S2T_EINVAL (the reference raises ValueError); G > 1 and diverse_strength negative or not
+     * finite -> S2T_ENOTSUP (a reward breaks the argument that a row's 2 * beam best are enough); G > 1 with step0_all_slots ->
+     * S2T_ENOTSUP.  diverse_strength is not looked at while G <= 1. */
+    int diverse_groups; float diverse_strength;
 } S2TDecodeDesc;
 
 /* Fragment-major copies for the MFMA B operand: lane l of fragment (tile, step) holds rows 16 tile + (l & 15), columns ks step + per (l >> 4) ..
@@ -503,7 +514,7 @@ int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDecodeRules* 
 /* The same three calls for an ensemble.  d: a HOST array of n HOST descriptors (and their HOST layer arrays), read during the call only.
  * Members may differ in D, heads, layers, ffn, ffn_slices, Ts, Tsp, enc_klen, embed_scale, ln_eps, gelu and in every weight and buffer
  * of their own (x0, x1, part0, part1, xn, logits, the layers' caches); they must agree on dtype, B, beam, V, ldv, max_len, min_len, pad,
- * unk, eos, step0_all_slots, unk_penalty, inv_temperature and on every state pointer (steps, anc, tok_hist, par_hist, cum_hist, blacklist,
+ * unk, eos, step0_all_slots, unk_penalty, inv_temperature, diverse_groups, diverse_strength and on every state pointer (steps, anc, tok_hist, par_hist, cum_hist, blacklist,
  * nfin, finished, fin_step, fin_row, fin_score, cand_val, cand_idx, init_scores).  Checked before any launch, in this order: d == NULL,
  * n < 1, n > 8 or a NULL d[j] -> S2T_EINVAL; `r` as s2t_decode_step_rules checks it (begin: no rules); members that disagree on a shared
  * field -> S2T_EINVAL; every member as s2t_decode_step checks it (S2T_ENOTSUP outside the limits).  graph_create checks graph_exec and
