@@ -14,6 +14,7 @@
 // and never stored).  Per-head / per-slice shares of the two output projections and of fc2 are written as f32 slabs and summed, in a
 // fixed order, by the NEXT phase's prologue together with residual and bias: deterministic, no atomics, no extra launch.
 #include "common.hpp"
+#include "sample.hpp"
 #include "s2t_hip.h"
 
 // Diagnostic build only (make dec_stamps: -DS2T_DEC_STAMPS): shader-clock stamps of workgroup (0, 0), wave 0 at the phase boundaries of
@@ -1003,15 +1004,28 @@ struct RowRuleArgs : RowArgs { int ngram, prefix_len, maxpos; const int* prefix;
 // pass requests a member's VPT columns together: the members' lse; the column maxima; the column sums.  2 VPT values in registers.
 constexpr int ENS_MAX = 8;
 struct RowEnsArgs : RowRuleArgs { int n_mem; float log_n; const float* mem[ENS_MAX]; };
-template <bool RULES, bool ENS = false> struct RowArgsOf { typedef RowArgs type; };
-template <> struct RowArgsOf<true, false> { typedef RowRuleArgs type; };
-template <> struct RowArgsOf<true, true> { typedef RowEnsArgs type; };
+// SAMPLE (s2t_decode_step_sample; built on the RULES code, as ENS is): the sampling search of include/s2t_hip.h.  The row draws ONE token
+// from its log-probabilities after the rule loop (csrc/sample.hpp: the kept set and the Gumbel arg-max on the registers the row already
+// sits in) and writes it as its only candidate, entry 0 of its list, with lp[token] + the cumulative score; the search for the K2 best
+// is not compiled.  At step 0 every slot is live and reads the sentence's first row of logits (every member's).
+struct RowSample { int topk; float topp; unsigned long long key; };
+struct RowRuleSampleArgs : RowRuleArgs { RowSample smp; };
+struct RowEnsSampleArgs : RowEnsArgs { RowSample smp; };
+template <bool RULES, bool ENS = false, bool SAMPLE = false> struct RowArgsOf { typedef RowArgs type; };
+template <> struct RowArgsOf<true, false, false> { typedef RowRuleArgs type; };
+template <> struct RowArgsOf<true, true, false> { typedef RowEnsArgs type; };
+template <> struct RowArgsOf<true, false, true> { typedef RowRuleSampleArgs type; };
+template <> struct RowArgsOf<true, true, true> { typedef RowEnsSampleArgs type; };
+__device__ __forceinline__ RowSample row_sample(const RowArgs&) { return RowSample{0, 0.f, 0ull}; }
+__device__ __forceinline__ RowSample row_sample(const RowRuleSampleArgs& a) { return a.smp; }
+__device__ __forceinline__ RowSample row_sample(const RowEnsSampleArgs& a) { return a.smp; }
 constexpr int ROW_HIST = 1024;                                     // positions of a history (max_len + 1 <= 1024), and words of the ban bitmap (V <= 32768)
 __device__ __forceinline__ bool cand_after(float v, int i, float lv, int li) { return v < lv || (v == lv && i > li); }
 __device__ __forceinline__ bool cand_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-template <int VPT, bool RULES, bool ENS = false>
-__global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RULES, ENS>::type a) {
+template <int VPT, bool RULES, bool ENS = false, bool SAMPLE = false>
+__global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RULES, ENS, SAMPLE>::type a) {
     static_assert(!ENS || RULES, "the ensemble row is built on the RULES variant");
+    static_assert(!SAMPLE || RULES, "the sampling row is built on the RULES variant");
     __shared__ float sh[16];
     [[maybe_unused]] float* const lse_s = sh + 8;                    // ENS: the members' normalisers (the block reductions use sh[0 .. 3])
     __shared__ float wv[4 * 32];
@@ -1046,7 +1060,8 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
             for (int i = tid; i < (V + 31) / 32; i += NTHREADS) ban_s[i] = 0u;
         }
     }
-    const float* x = a.logits + (size_t)n * a.ldv;                   // ENS: member 0's
+    const int nl = (SAMPLE && t == 0) ? s * a.beam : n;              // the row of logits: SAMPLE at step 0, the sentence's first
+    const float* x = a.logits + (size_t)nl * a.ldv;                  // ENS: member 0's
     float val[VPT];
     float m = -INFINITY;
 #pragma unroll
@@ -1069,7 +1084,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
         const int nm = a.n_mem;
         if (tid == 0) lse_s[0] = lse;
         for (int j = 1; j < nm; ++j) {                               // the other members' normalisers, in the arithmetic above
-            const float* xj = a.mem[j] + (size_t)n * a.ldv;
+            const float* xj = a.mem[j] + (size_t)nl * a.ldv;
             float mj = -INFINITY;
 #pragma unroll
             for (int i = 0; i < VPT; ++i) {
@@ -1093,7 +1108,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
 #pragma unroll
         for (int i = 0; i < VPT; ++i) val[i] = -INFINITY;
         for (int j = 0; j < nm; ++j) {
-            const float* xj = a.mem[j] + (size_t)n * a.ldv;
+            const float* xj = a.mem[j] + (size_t)nl * a.ldv;
             const float l = lse_s[j];
 #pragma unroll
             for (int i = 0; i < VPT; ++i) val[i] = fmaxf(val[i], __fmul_rn(xj[min(tid + i * NTHREADS, V - 1)], a.it) - l);
@@ -1102,7 +1117,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
 #pragma unroll
         for (int i = 0; i < VPT; ++i) sm[i] = 0.f;
         for (int j = 0; j < nm; ++j) {
-            const float* xj = a.mem[j] + (size_t)n * a.ldv;
+            const float* xj = a.mem[j] + (size_t)nl * a.ldv;
             const float l = lse_s[j];
 #pragma unroll
             for (int i = 0; i < VPT; ++i) sm[i] += expf((__fmul_rn(xj[min(tid + i * NTHREADS, V - 1)], a.it) - l) - val[i]);
@@ -1129,7 +1144,7 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
             __syncthreads();
         }
     }
-    const bool live = t > 0 || a.step0_all || (n % a.beam) == 0;          // step 0: every slot holds the same <bos> (search.py:64-66)
+    [[maybe_unused]] const bool live = t > 0 || a.step0_all || (n % a.beam) == 0;          // step 0: every slot holds the same <bos> (search.py:64-66)
     const float base = t > 0 ? a.cum_hist[(size_t)t * a.N + n] : (a.init_scores ? a.init_scores[n] : 0.f);
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
@@ -1145,7 +1160,20 @@ __global__ __launch_bounds__(NTHREADS) void dec_row_kernel(typename RowArgsOf<RU
         if constexpr (RULES) {
             if (blocking && v < V && ((ban_s[v >> 5] >> (v & 31)) & 1u)) lp = -INFINITY;
         }
-        val[i] = (live && v < V) ? lp + base : -INFINITY;
+        if constexpr (SAMPLE) val[i] = v < V ? lp + 0.f : -INFINITY;      // the draw is from lp alone (-0 is +0: one image per value)
+        else val[i] = (live && v < V) ? lp + base : -INFINITY;
+    }
+    if constexpr (SAMPLE) {
+        __shared__ smp::Scratch sc;
+        const RowSample sp = row_sample(a);
+        int turn = 0;
+        const smp::Kept kept = smp::kept_set<VPT, NTHREADS>(val, V, sp.topk, sp.topp, sc, turn);
+        bool mine;
+        float lp_tok;
+        const int tok = smp::draw<VPT, NTHREADS>(val, kept, smp::row_key(sp.key, t, n), sc, turn, mine, lp_tok);
+        if (mine) { a.cand_val[(size_t)n * a.K2] = lp_tok + base; a.cand_idx[(size_t)n * a.K2] = tok; }
+        DSTAMP(3, 6);
+        return;
     }
     // K2 best of the row.  Threshold first: every lane's largest value; the K2-th largest lane maximum of a wave is a value that at
     // least K2 columns reach, so the largest such value over the four waves (`thr`) is a lower bound of the row's K2-th best: only
@@ -1305,8 +1333,12 @@ __device__ __forceinline__ SentMember ens_member(const SentEnsArgs& a, int j) {
 // penalised entries lie among its 2 beam best unpenalised ones: the lists the row launch writes are enough, for any strength >= 0.
 // One wave: a lane holds up to four of the group's <= 8 x 32 entries; the taken tokens are read from the lanes that keep them (rank =
 // lane) by scalar broadcasts; 2 mg arg-max rounds per group, 2 beam in all as in the merge.
-template <typename T, bool ENS = false, bool DIV = false>
+// SAMPLE (the sampling search, with the SAMPLE form of the row launch): exactly `beam` candidates, candidate r = the one entry slot r's
+// row launch wrote, its parent slot r (slot 0 at step 0: search.py:269-272); everything behind the forming of the candidates is the
+// code of the beam search run with k = beam.
+template <typename T, bool ENS = false, bool DIV = false, bool SAMPLE = false>
 __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<ENS, DIV>::type a) {
+    static_assert(!(DIV && SAMPLE), "a sampling search has no groups");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ __attribute__((aligned(16))) float l_val[16 * 32];
     __shared__ __attribute__((aligned(16))) int l_idx[16 * 32];
@@ -1318,14 +1350,14 @@ __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<
     DSTAMP(4, 0);
     const bool first = t == 0 && !a.step0_all;
     const long ncols = first ? a.V : (long)beam * a.V;
-    const int k = (int)min((long)K2, ncols - 1);                   // search.py:71-75: pad is never selected
+    const int k = SAMPLE ? beam : (int)min((long)K2, ncols - 1);   // search.py:71-75: pad is never selected
     const int rows = first ? 1 : beam;
     // everything this launch reads is requested at once: the rows' candidate lists, the sentence's flags, its ancestor rows
-    const int ne = rows * K2;                                      // <= 512 entries: two per thread
+    const int ne = SAMPLE ? 0 : rows * K2;                         // <= 512 entries: two per thread
     float ev[2]; int ei[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int i = min(tid + u * NTHREADS, ne - 1);
+        const int i = SAMPLE ? min(tid, beam - 1) * K2 : min(tid + u * NTHREADS, ne - 1);      // SAMPLE: entry 0 of slot tid's list
         ev[u] = a.cand_val[(size_t)n0 * K2 + i]; ei[u] = a.cand_idx[(size_t)n0 * K2 + i];
     }
     int bl = 0, done = 0, nf = 0;
@@ -1356,7 +1388,9 @@ __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<
         // the entries before it over the lists in LDS 10,700; the same count through scalar broadcasts of one entry per lane 11,300.)
         [[maybe_unused]] int head = 0;                             // (declared here, before my_val, as ever: the plain forms' registers stay put)
         float my_val = -INFINITY; int my_tok = 0, my_row = n0;
-        if constexpr (DIV) {
+        if constexpr (SAMPLE) {
+            if (tid < beam) { my_val = ev[0]; my_tok = ei[0]; my_row = first ? n0 : n0 + tid; }
+        } else if constexpr (DIV) {
             const int G = a.div_groups, mg = beam / G, kg = 2 * mg;        // k == K2 == G * kg (V >= 2 beam + 1: desc_ok)
             const int ne_g = (first ? 1 : mg) * K2;                        // a group's entries: <= 8 rows x 32 = 4 per lane
             for (int g = 0; g < G; ++g) {
@@ -1581,6 +1615,7 @@ template <typename T> hipError_t configure() {
     }
     DEC_ALLOW(dec_sent_kernel<T>); DEC_ALLOW((dec_sent_kernel<T, true>));
     DEC_ALLOW((dec_sent_kernel<T, false, true>)); DEC_ALLOW((dec_sent_kernel<T, true, true>));
+    DEC_ALLOW((dec_sent_kernel<T, false, false, true>)); DEC_ALLOW((dec_sent_kernel<T, true, false, true>));
     DEC_ALLOW((dec_logits_kernel<T, 1>)); DEC_ALLOW((dec_logits_kernel<T, 2>)); DEC_ALLOW((dec_logits_kernel<T, 3>)); DEC_ALLOW((dec_logits_kernel<T, 4>));
     DEC_ALLOW((dec_logits_kernel<T, 5>)); DEC_ALLOW((dec_logits_kernel<T, 6>)); DEC_ALLOW((dec_logits_kernel<T, 7>)); DEC_ALLOW((dec_logits_kernel<T, 8>));
     return hipSuccess;
@@ -1703,14 +1738,27 @@ void sent_args(const S2TDecodeDesc* d, SentArgs& a) {
         if (vpt <= 8) DEC_ROW(8); else if (vpt <= 12) DEC_ROW(12); else if (vpt <= 16) DEC_ROW(16); else if (vpt <= 20) DEC_ROW(20); \
         else if (vpt <= 24) DEC_ROW(24); else if (vpt <= 32) DEC_ROW(32); else if (vpt <= 40) DEC_ROW(40); else if (vpt <= 48) DEC_ROW(48); \
         else if (vpt <= 64) DEC_ROW(64); else if (vpt <= 96) DEC_ROW(96); else DEC_ROW(128); } while (0)
-// r: the rules of s2t_decode_step_rules, or NULL (checked by rules_check)
+// r: the rules of s2t_decode_step_rules, or NULL (checked by rules_check); smp: the sampling search of s2t_decode_step_sample, or NULL
 template <typename T>
-int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
+int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st) {
     int launched = 0;
     const int rc = chain_impl<T>(d, st, launched);
     if (rc != S2T_OK) return rc == DEC_STOPPED ? S2T_OK : rc;
     const int B = d->B, N = B * d->beam;
     const LdsNeed need = lds_need(d);
+    if (smp) {
+        RowRuleSampleArgs a;
+        row_args(d, r, r && (r->no_repeat_ngram > 0 || r->prefix_len > 0), a);
+        a.smp = RowSample{smp->topk, smp->topp, smp->key};
+#define DEC_ROW(VPT_) hipLaunchKernelGGL((dec_row_kernel<VPT_, true, false, true>), dim3(N), dim3(NTHREADS), 0, st, a)
+        DEC_ROW_BY_VPT(d->V);
+#undef DEC_ROW
+        SentArgs b;
+        sent_args(d, b);
+        hipLaunchKernelGGL((dec_sent_kernel<T, false, false, true>), dim3(B), dim3(NTHREADS), need.sent, st, b);
+        S2T_LAUNCH_CHECK();
+        return S2T_OK;
+    }
     {
         RowRuleArgs a;
         const bool rules = r && (r->no_repeat_ngram > 0 || r->prefix_len > 0);
@@ -1735,7 +1783,7 @@ int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, hipStream_t st) {
 // buffers, one after the other on `st`, then ONE row launch over all the members' logits and ONE sentence launch that also writes every
 // member's next input.  The serial order is what makes the shared `steps` and `anc` safe: no member's chain runs beside the sentence launch.
 template <typename T>
-int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, hipStream_t st) {
+int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st) {
     int launched = 0;
     for (int j = 0; j < n; ++j) {
         const int rc = chain_impl<T>(dv[j], st, launched);
@@ -1744,14 +1792,21 @@ int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r
     const S2TDecodeDesc* d = dv[0];
     const int B = d->B, N = B * d->beam;
     {
-        RowEnsArgs a;
+        RowEnsSampleArgs a;
         const bool rules = r && (r->no_repeat_ngram > 0 || r->prefix_len > 0);
         row_args(d, r, rules, a);
         a.n_mem = n; a.log_n = logf((float)n);
         for (int j = 0; j < ENS_MAX; ++j) a.mem[j] = j < n ? dv[j]->logits : nullptr;
-#define DEC_ROW(VPT_) hipLaunchKernelGGL((dec_row_kernel<VPT_, true, true>), dim3(N), dim3(NTHREADS), 0, st, a)
-        DEC_ROW_BY_VPT(d->V);
+        if (smp) {
+            a.smp = RowSample{smp->topk, smp->topp, smp->key};
+#define DEC_ROW(VPT_) hipLaunchKernelGGL((dec_row_kernel<VPT_, true, true, true>), dim3(N), dim3(NTHREADS), 0, st, a)
+            DEC_ROW_BY_VPT(d->V);
 #undef DEC_ROW
+        } else {
+#define DEC_ROW(VPT_) hipLaunchKernelGGL((dec_row_kernel<VPT_, true, true>), dim3(N), dim3(NTHREADS), 0, st, static_cast<const RowEnsArgs&>(a))
+            DEC_ROW_BY_VPT(d->V);
+#undef DEC_ROW
+        }
     }
     {
         SentEnsDivArgs a;
@@ -1763,7 +1818,8 @@ int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r
             if (j < n) { o.embed = dv[j]->embed; o.pos_table = dv[j]->pos_table; o.x0 = dv[j]->x0; o.D = dv[j]->D; o.embed_scale = dv[j]->embed_scale; }
             else { o.embed = nullptr; o.pos_table = nullptr; o.x0 = nullptr; o.D = 0; o.embed_scale = 0.f; }
         }
-        if (d->diverse_groups > 1) hipLaunchKernelGGL((dec_sent_kernel<T, true, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, a);
+        if (smp) hipLaunchKernelGGL((dec_sent_kernel<T, true, false, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, static_cast<const SentEnsArgs&>(a));
+        else if (d->diverse_groups > 1) hipLaunchKernelGGL((dec_sent_kernel<T, true, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, a);
         else hipLaunchKernelGGL((dec_sent_kernel<T, true>), dim3(B), dim3(NTHREADS), lds_need(d).sent, st, static_cast<const SentEnsArgs&>(a));
     }
     S2T_LAUNCH_CHECK();
@@ -1845,7 +1901,7 @@ extern "C" int s2t_decode_step_rules(const S2TDecodeDesc* d, const S2TDecodeRule
     if (rc != S2T_OK) return rc;
     rc = decode_check(d);
     if (rc != S2T_OK) return rc;
-    return d->dtype == S2T_BF16 ? step_impl<bf16>(d, r, (hipStream_t)stream) : step_impl<float>(d, r, (hipStream_t)stream);
+    return d->dtype == S2T_BF16 ? step_impl<bf16>(d, r, nullptr, (hipStream_t)stream) : step_impl<float>(d, r, nullptr, (hipStream_t)stream);
 }
 extern "C" int s2t_decode_step(const S2TDecodeDesc* d, void* stream) { return s2t_decode_step_rules(d, nullptr, stream); }
 
@@ -1873,8 +1929,8 @@ static int ensemble_check(const S2TDecodeDesc* const* dv, int n, const S2TDecode
     return S2T_OK;
 }
 template <typename T>
-static int step_any(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, hipStream_t st) {
-    return n == 1 ? step_impl<T>(dv[0], r, st) : step_ens_impl<T>(dv, n, r, st);
+static int step_any(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st) {
+    return n == 1 ? step_impl<T>(dv[0], r, smp, st) : step_ens_impl<T>(dv, n, r, smp, st);
 }
 
 extern "C" int s2t_decode_begin_ensemble(const S2TDecodeDesc* const* dv, int n, int bos, void* stream) {
@@ -1890,7 +1946,20 @@ extern "C" int s2t_decode_begin_ensemble(const S2TDecodeDesc* const* dv, int n, 
 extern "C" int s2t_decode_step_ensemble(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, void* stream) {
     const int rc = ensemble_check(dv, n, r);
     if (rc != S2T_OK) return rc;
-    return dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, (hipStream_t)stream) : step_any<float>(dv, n, r, (hipStream_t)stream);
+    return dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, nullptr, (hipStream_t)stream) : step_any<float>(dv, n, r, nullptr, (hipStream_t)stream);
+}
+// the checks of the *_sample calls, in the order include/s2t_hip.h documents
+static int sample_check(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s) {
+    if (!s || s->topk < 0 || s->topp != s->topp) return S2T_EINVAL;
+    const int rc = ensemble_check(dv, n, r);
+    if (rc != S2T_OK) return rc;
+    if (dv[0]->diverse_groups > 1 || dv[0]->step0_all_slots) return S2T_ENOTSUP;
+    return S2T_OK;
+}
+extern "C" int s2t_decode_step_sample(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, void* stream) {
+    const int rc = sample_check(dv, n, r, s);
+    if (rc != S2T_OK) return rc;
+    return dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, s, (hipStream_t)stream) : step_any<float>(dv, n, r, s, (hipStream_t)stream);
 }
 
 extern "C" int s2t_decode_prepare_enc(int dtype, const void* kv_enc, void* kp_enc, void* vp_enc, int Ts, int Tsp, int B, int D, int heads, void* stream) {
@@ -1918,8 +1987,8 @@ extern "C" int s2t_decode_pack_weight(int dtype, const void* W, int ldw, int N, 
     return S2T_OK;
 }
 
-// n_steps x step_any(dv, n, r) recorded on a private stream as one chain and instantiated; the arguments are checked by the callers
-static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
+// n_steps x step_any(dv, n, r, smp) recorded on a private stream as one chain and instantiated; the arguments are checked by the callers
+static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, int n_steps, void** graph_exec) {
     hipStream_t cs = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
     if (e != hipSuccess) return S2T_EHIP(e);
@@ -1928,7 +1997,7 @@ static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRu
     int out = S2T_OK;
     e = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed);
     if (e == hipSuccess) {
-        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, cs) : step_any<float>(dv, n, r, cs);
+        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, smp, cs) : step_any<float>(dv, n, r, smp, cs);
         e = hipStreamEndCapture(cs, &g);
     }
     if (e == hipSuccess && out == S2T_OK) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
@@ -1947,14 +2016,22 @@ extern "C" int s2t_decode_graph_create_rules(const S2TDecodeDesc* d, const S2TDe
     if (rc != S2T_OK) return rc;
     rc = decode_check(d);
     if (rc != S2T_OK) return rc;
-    return graph_record(&d, 1, r, n_steps, graph_exec);
+    return graph_record(&d, 1, r, nullptr, n_steps, graph_exec);
 }
 extern "C" int s2t_decode_graph_create_ensemble(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, int n_steps, void** graph_exec) {
     if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
     *graph_exec = nullptr;
     const int rc = ensemble_check(dv, n, r);
     if (rc != S2T_OK) return rc;
-    return graph_record(dv, n, r, n_steps, graph_exec);
+    return graph_record(dv, n, r, nullptr, n_steps, graph_exec);
+}
+extern "C" int s2t_decode_graph_create_sample(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, int n_steps,
+                                              void** graph_exec) {
+    if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
+    *graph_exec = nullptr;
+    const int rc = sample_check(dv, n, r, s);
+    if (rc != S2T_OK) return rc;
+    return graph_record(dv, n, r, s, n_steps, graph_exec);
 }
 extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec) {
     return s2t_decode_graph_create_rules(d, nullptr, n_steps, graph_exec);

@@ -14,7 +14,8 @@ score rules and one sentence launch does the bookkeeping and embeds the chosen t
 
 `SequenceGenerator` (sequence_generator.py) takes this path for one model or an ensemble with the plain, the hierarchical or the
 group-diverse beam search (`diverse_groups`: the per-sentence launch forms the groups' penalised candidates from the same row lists), with n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch
-(`s2t_decode_step_rules`), and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for attention output,
+(`s2t_decode_step_rules`), or with the sampling search (`sampling`: each row draws its one candidate inside the per-row launch,
+`s2t_decode_step_sample`), and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for attention output,
 a prefix that holds EOS, n-gram size 1, members of different dtypes and any member outside the shape limits.
 """
 import ctypes
@@ -132,10 +133,13 @@ class EnsembleDecodeSession:
     descriptor names it; `members[j].bufs` / `bufs_of[j]` are member j's own buffers.  `ok` False: a member, the rules or the
     combination is refused and nothing ran.  diverse_groups G > 1: group-diverse beam search (fairseq/search.py:103-161) with
     diverse_strength >= 0, a form of the per-sentence launch (G must divide the beam; not with step0_all_slots); 0 or 1: plain.
+    sampling: None, or dict(topk, topp, key) -- the sampling search (fairseq/search.py:164-278; the draw of include/s2t_hip.h
+    S2TDecodeSample): forms of the per-row and per-sentence launches behind s2t_decode_step_sample / s2t_decode_graph_create_sample;
+    not with diverse_groups > 1 nor step0_all_slots.  None launches exactly what was launched before.
     The other arguments as BeamDecodeSession's."""
 
     def __init__(self, members, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0, init_scores=None,
-                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0, diverse_strength=0.5):
+                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0, diverse_strength=0.5, sampling=None):
         members = list(members)
         assert members, "an ensemble needs at least one member"
         engine, enc_out = members[0][0], members[0][2]
@@ -151,6 +155,14 @@ class EnsembleDecodeSession:
         G, lam = int(diverse_groups), float(diverse_strength)
         if G < 0 or (G > 1 and (beam % G != 0 or not (lam >= 0.0 and math.isfinite(lam)) or step0_all_slots)):
             self.ok = False                                             # what the C ABI refuses (include/s2t_hip.h: diverse_groups)
+        self.sample, self.sample_addr = None, None                      # S2TDecodeSample of a sampling search
+        if sampling is not None:
+            topk, topp = int(sampling.get("topk", 0)), float(sampling.get("topp", 0.0))
+            if G > 1 or step0_all_slots or topk < 0 or topp != topp:
+                self.ok = False                                         # (include/s2t_hip.h: s2t_decode_step_sample)
+            sm = self.sample = L.DecodeSample()
+            sm.topk, sm.topp, sm.key = max(topk, 0), topp, int(sampling.get("key", 0)) & 0xFFFFFFFFFFFFFFFF
+            self.sample_addr = ctypes.addressof(sm)
         if not self.ok:
             return
         sh = dict(beam=beam, max_len=max_len, min_len=min_len, pad=pad, unk=unk, eos=eos, V=V, unk_penalty=unk_penalty, temperature=temperature,
@@ -231,7 +243,10 @@ class EnsembleDecodeSession:
             L.check(lib.s2t_decode_begin_ensemble(self.descs_addr, n, int(bos), st), "s2t_decode_begin_ensemble")
         exec_ = ctypes.c_void_p(0)
         per = POLL_STEPS if graph else 1                    # steps per launch: one recorded graph holds POLL_STEPS of them
-        if graph and not one:
+        if graph and self.sample_addr:
+            L.check(lib.s2t_decode_graph_create_sample(self.descs_addr, n, self.rules_addr, self.sample_addr, per, ctypes.addressof(exec_)),
+                    "s2t_decode_graph_create_sample")
+        elif graph and not one:
             L.check(lib.s2t_decode_graph_create_ensemble(self.descs_addr, n, self.rules_addr, per, ctypes.addressof(exec_)),
                     "s2t_decode_graph_create_ensemble")
         elif graph and self.rules_addr:
@@ -245,6 +260,8 @@ class EnsembleDecodeSession:
             while steps < self.max_len + 1:
                 if graph:
                     L.check(lib.s2t_decode_graph_launch(exec_.value, st), "s2t_decode_graph_launch")
+                elif self.sample_addr:
+                    L.check(lib.s2t_decode_step_sample(self.descs_addr, n, self.rules_addr, self.sample_addr, st), "s2t_decode_step_sample")
                 elif not one:
                     L.check(lib.s2t_decode_step_ensemble(self.descs_addr, n, self.rules_addr, st), "s2t_decode_step_ensemble")
                 elif self.rules_addr:
@@ -294,10 +311,10 @@ class BeamDecodeSession(EnsembleDecodeSession):
 
     def __init__(self, engine, pfx, enc_out, enc_klen, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0,
                  init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0,
-                 diverse_strength=0.5):
+                 diverse_strength=0.5, sampling=None):
         super().__init__([(engine, pfx, enc_out, enc_klen)], beam, max_len, min_len, pad, unk, eos, V, unk_penalty, temperature,
                          init_scores=init_scores, step0_all_slots=step0_all_slots, no_repeat_ngram_size=no_repeat_ngram_size,
-                         prefix_tokens=prefix_tokens, diverse_groups=diverse_groups, diverse_strength=diverse_strength)
+                         prefix_tokens=prefix_tokens, diverse_groups=diverse_groups, diverse_strength=diverse_strength, sampling=sampling)
         if self.members:
             m = self.members[0]
             self.desc, self.addr, self.layers = m.desc, m.addr, m.layers

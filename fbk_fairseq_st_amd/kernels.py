@@ -537,6 +537,20 @@ def topk(logits, k):
     return vals, idx
 
 
+def sample_rows(lprobs, draws, topk, topp, key, step):
+    """the draws of the sampling search (include/s2t_hip.h s2t_sample_rows): f32 [rows, V] log-probabilities (row stride may be padded),
+    row r / draw j = slot r * draws + j -> (int32 [rows, draws] tokens, f32 [rows, draws] their log-probabilities, int32 [rows] sizes
+    of the kept sets)"""
+    rows, V = lprobs.shape
+    assert lprobs.dtype == torch.float32
+    tok = torch.empty((rows, draws), dtype=torch.int32, device=lprobs.device)
+    lp = torch.empty((rows, draws), dtype=torch.float32, device=lprobs.device)
+    n_kept = torch.empty((rows,), dtype=torch.int32, device=lprobs.device)
+    L.check(_lib().s2t_sample_rows(L.ptr(lprobs), rows, V, _row_ld(lprobs), int(draws), int(topk), float(topp), int(key), int(step),
+                                   L.ptr(tok), L.ptr(lp), L.ptr(n_kept), L.stream()), "s2t_sample_rows")
+    return tok, lp, n_kept
+
+
 def log_softmax(logits, temperature=1.0):
     """[rows,V] (row stride may be padded) -> f32 [rows,V] log-probabilities"""
     rows, V = logits.shape

@@ -110,6 +110,9 @@ SIGNATURES = {
     "s2t_decode_begin_ensemble": [P, c_int, c_int, P],
     "s2t_decode_step_ensemble": [P, c_int, P, P],
     "s2t_decode_graph_create_ensemble": [P, c_int, P, c_int, P],
+    "s2t_decode_step_sample": [P, c_int, P, P, P],
+    "s2t_decode_graph_create_sample": [P, c_int, P, P, c_int, P],
+    "s2t_sample_rows": [P, c_long, c_int, c_int, c_int, c_int, c_float, c_ull, c_int, P, P, P, P],
     "s2t_decode_graph_launch": [P, P],
     "s2t_decode_graph_destroy": [P],
     "s2t_host_batch_by_size": [P, c_longlong, P, c_longlong, c_longlong, c_int, P, P, P],
@@ -168,6 +171,11 @@ class DecodeDesc(ctypes.Structure):
 class DecodeRules(ctypes.Structure):
     """S2TDecodeRules of include/s2t_hip.h"""
     _fields_ = [("no_repeat_ngram", c_int), ("prefix_len", c_int), ("prefix", c_void_p)]
+
+
+class DecodeSample(ctypes.Structure):
+    """S2TDecodeSample of include/s2t_hip.h"""
+    _fields_ = [("topk", c_int), ("topp", c_float), ("key", c_ull)]
 
 
 _lib = None

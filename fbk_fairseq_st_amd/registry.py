@@ -354,7 +354,10 @@ class FairseqTask(_TaskBase):
         groups, rate = getattr(args, "diverse_beam_groups", -1), getattr(args, "diversity_rate", -1)
         if sum(int(bool(c)) for c in (sampling, groups > 0, match_source_len, rate > 0)) > 1:       # fairseq_task.py:252-264
             raise ValueError("Provided Search parameters are mutually exclusive.")
-        for flag in ("score_reference", "sampling", "match_source_len"):
+        if sampling:
+            raise NotImplementedError("--sampling is not opened through build_generator yet: hand SequenceGenerator a "
+                                      "search_strategy=sequence_generator.Sampling(tgt_dict, sampling_topk, sampling_topp, seed=...)")
+        for flag in ("score_reference", "match_source_len"):
             if getattr(args, flag, False):
                 raise NotImplementedError("--%s is outside the S2T hot path" % flag.replace("_", "-"))
         if rate > 0:

@@ -19,7 +19,10 @@ tokens without EOS included: both are score rules of its per-row kernel, which f
 probability.  The step-by-step loop below serves `retain_attention`, `--layernorm-embedding`, n-gram size 1, a prefix that holds EOS,
 ensembles whose members differ in compute dtype or hold a member outside the device route's shape limits (and S2T_DEVICE_SEARCH=0); with `retain_attention=True` every hypothesis carries its `attention` (src_len x tgt_len, the last decoder layer's
 encoder-attention averaged over heads and ensemble members: sequence_generator.py:286-292,510-560,757-768) and, with `print_alignment`, the
-hard `alignment` generate.py prints (utils.extract_hard_alignment, fairseq/utils.py); sampling is not part of this path.
+hard `alignment` generate.py prints (utils.extract_hard_alignment, fairseq/utils.py).
+The sampling search (`Sampling`, fairseq/search.py:164-278: unrestricted, top-k, nucleus) runs device-resident as well -- forms of the
+per-row and per-sentence launches that draw one token per row with a stateless Gumbel-max draw -- and through `kernels.sample_rows` on
+the step-by-step loop, which serves a hierarchical start besides the cases above.
 Group-diverse beam search (`DiverseBeamSearch`, --diverse-beam-groups: fairseq/search.py:103-161) runs device-resident too for a
 strength >= 0 -- the groups' penalised selections are made from the rows' 2 * beam best by the per-sentence launch -- and on the
 step-by-step loop for a negative strength.  `TwoPhaseSequenceGenerator` runs the same loop twice for dual-decoder
@@ -27,9 +30,11 @@ models: transcripts with the auxiliary decoder, then translations seeded by the 
 """
 import math
 
+import numpy as np
 import torch
 
 from . import kernels as K
+from . import sampling as SMP
 
 
 class BeamSearch:
@@ -99,6 +104,69 @@ class DiverseBeamSearch:
         return (torch.stack(out_s, 2).view(B, k * G), torch.stack(out_i, 2).view(B, k * G), torch.stack(out_b, 2).view(B, k * G))
 
 
+class Sampling:
+    """fairseq/search.py:164-278: every hypothesis slot draws ONE token per step -- from all columns, from the `sampling_topk` best, or
+    from the nucleus of mass `sampling_topp` (which takes precedence) -- so a step has exactly `beam` candidates: candidate r is slot r's
+    draw, its parent slot r; at step 0 every slot draws from the sentence's first row and the parent is slot 0.  Nothing is renormalised.
+    The draw is not torch.multinomial, whose stream cannot be reproduced, but the stateless function of (key, step, slot, column) that
+    include/s2t_hip.h describes (Gumbel-max over the kept set; sampling.py restates it): the same on host tensors (numpy), on device
+    tensors (`kernels.sample_rows`) and inside the device-resident search (decode.py, `sampling`).  key = (seed, number of `generate`
+    calls so far): a generator built with the same seed repeats its sequence of calls.  Deviations from the reference: the score is
+    lp[token] itself (the reference: log(exp(lp)), at most 1 ulp away); a row without a finite column gives token 0 with score -inf
+    (the reference raises)."""
+
+    def __init__(self, tgt_dict, sampling_topk=-1, sampling_topp=-1.0, seed=1):
+        self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        self.sampling_topk, self.sampling_topp = int(sampling_topk), float(sampling_topp)
+        self.seed, self.calls = int(seed), 0
+
+    def new_call(self):
+        """SequenceGenerator.generate: the next call's draws are independent of this one's"""
+        self.calls += 1
+
+    @property
+    def topk(self):
+        return max(self.sampling_topk, 0)
+
+    @property
+    def topp(self):
+        return self.sampling_topp if self.sampling_topp > 0 else 0.0
+
+    @property
+    def key(self):
+        return SMP.make_key(self.seed, self.calls)
+
+    def _choose(self, step, lp, keep, slot):
+        """host route: the token slot `slot` draws from row lp (float32 [V]) with kept set keep (bool [V])"""
+        return SMP.draw(lp, keep, self.key, step, slot)
+
+    def step(self, step, lprobs, scores, prev_scores=None):
+        """lprobs f32 [B, beam, V]; scores [B, beam, >=step] cumulative.  Returns (scores, token ids, beam ids), each [B, beam].
+        prev_scores [B, beam, 1] (a hierarchical start, step-by-step route only): the slots differ from step 0 on, so each draws from
+        its own row there and continues itself, from its own start score."""
+        B, beam, V = lprobs.shape
+        dev = lprobs.device
+        first = step == 0 and prev_scores is None
+        rows = lprobs[:, 0, :] if first else lprobs.reshape(B * beam, V)
+        draws = beam if first else 1
+        if lprobs.is_cuda:
+            tok, lp, _ = K.sample_rows(rows, draws, self.topk, self.topp, self.key, step)
+            tok, lp = tok.view(B, beam).to(torch.int64), lp.view(B, beam)
+        else:
+            r = rows.numpy()
+            tok_n, lp_n = np.zeros((r.shape[0], draws), np.int64), np.zeros((r.shape[0], draws), np.float32)
+            for i in range(r.shape[0]):
+                keep = SMP.kept_set(r[i], self.topk, self.topp)
+                for j in range(draws):
+                    t = self._choose(step, r[i], keep, i * draws + j)
+                    tok_n[i, j], lp_n[i, j] = t, (r[i, t] if keep.any() else -np.inf)
+            tok, lp = torch.from_numpy(tok_n).view(B, beam), torch.from_numpy(lp_n).view(B, beam)
+        if first:
+            return lp, tok, torch.zeros((B, beam), dtype=torch.int64, device=dev)
+        return lp + (prev_scores[:, :, 0] if step == 0 else scores[:, :, step - 1]), tok, torch.arange(beam, device=dev).repeat(B, 1)
+
+
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True, len_penalty=1.0,
                  unk_penalty=0.0, retain_dropout=False, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
@@ -133,6 +201,8 @@ class SequenceGenerator:
         was_training = [m.training for m in self.models]                  # the reference also ignores `models` here (:149-161)
         for m in self.models:
             m.eval()                                                      # sequence_generator.py:86-87
+        if isinstance(self.search, Sampling):
+            self.search.new_call()
         try:
             return self._generate(self.models[0], sample, bos_token, prefix_tokens=prefix_tokens)
         finally:
@@ -188,9 +258,13 @@ class SequenceGenerator:
         EOS (the reference then copies slot 0 over the sentence's other slots, :449-476), members of different compute dtypes, or a
         shape the session refuses for any member."""
         from . import decode as DEC
-        if not DEC.device_search_enabled() or type(search) not in (BeamSearch, HierarchicalBeamSearch, DiverseBeamSearch):
+        if not DEC.device_search_enabled() or type(search) not in (BeamSearch, HierarchicalBeamSearch, DiverseBeamSearch, Sampling):
             return None
         div = {}
+        if type(search) is Sampling:
+            if prev_scores is not None:                                    # a hierarchical start makes every slot of step 0 its own row
+                return None
+            div = dict(sampling=dict(topk=search.topk, topp=search.topp, key=search.key))
         if type(search) is DiverseBeamSearch:
             if self.beam_size % search.num_groups != 0:
                 raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")

@@ -525,6 +525,35 @@ int s2t_decode_step_ensemble(const S2TDecodeDesc* const* d, int n, const S2TDeco
 int s2t_decode_graph_create_ensemble(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, int n_steps, void** graph_exec);
 int s2t_decode_graph_launch(void* graph_exec, void* stream);
 int s2t_decode_graph_destroy(void* graph_exec);
+/* ---- sampling search (fairseq/search.py:164-278 Sampling: unrestricted, top-k, nucleus) --------------------------------------------
+ * torch.multinomial's stream cannot be reproduced, so the draw is a stateless function, the same in every call below (csrc/sample.hpp):
+ *   uniform   h = hash32(key, step t, slot n, column v) -- 32-bit integer arithmetic only --, u = ((h >> 9) + 0.5) * 2^-23: exact in f32,
+ *             never 0 or 1;
+ *   kept set  of a row of log-probabilities lp (after all score rules, NOT renormalised), in the order value descending, column
+ *             ascending: topp > 0 (takes precedence): a column is kept iff the mass expf(lp) strictly before it is < topp (topp >= the
+ *             total mass keeps every finite column); else topk > 0: the first topk columns (topk >= the number of finite columns keeps
+ *             them all); else every finite column.  -inf columns are never kept;
+ *   token     the arg-max over the kept columns of lp + g, g = -logf(-logf(u)) (Gumbel-max; value descending, column ascending on ties);
+ *             its score is lp[token] itself -- the reference returns log(exp(lp)), at most 1 ulp away.  A row without a finite column
+ *             gives token 0 with score -inf (the reference raises there).
+ * s2t_sample_rows: lprobs f32 [rows][V] with row stride ld; row r, draw j < draws is slot n = r * draws + j: tok / lp_out [rows * draws],
+ * n_kept[r] the size of row r's kept set.  Checked before any launch: a NULL pointer, rows < 1, draws < 1, topk < 0, topp NaN, V < 1,
+ * ld < V, step < 0 -> S2T_EINVAL; V > 32768 -> S2T_ENOTSUP. */
+int s2t_sample_rows(const float* lprobs, long rows, int V, int ld, int draws, int topk, float topp, unsigned long long key, int step,
+                    int* tok, float* lp_out, int* n_kept, void* stream);
+/* The device-resident search with that draw instead of the merge: a form of the per-row launch (built on the rules form: prefix tokens and
+ * n-gram blocking apply before the draw; an ensemble draws from the log of the members' mean probability) and of the per-sentence launch;
+ * the number of launches does not change.  Slot n = s * beam + j draws its own token at every step, from its own row -- at step 0 from the
+ * sentence's FIRST row (every member's), with parent slot 0 -- and candidate r of a sentence is slot r's draw: exactly `beam` candidates,
+ * score = lp[token] + the slot's cumulative score, which enters neither the keys nor the kept set.  EOS finalisation, black-listing, the
+ * records and the next input are those of the beam search run with `beam` candidates.  The step index of the hash is steps[s]: one
+ * recorded graph serves every step.  topk 0 = off, topp <= 0 = off.  n = 1..8 members; begin, launch and destroy are the calls above.
+ * Checked before any launch, in this order: s == NULL, topk < 0 or topp NaN -> S2T_EINVAL; everything s2t_decode_step_ensemble checks, in
+ * its order; diverse_groups > 1 or step0_all_slots -> S2T_ENOTSUP.  graph_create checks graph_exec and n_steps first, as above. */
+typedef struct S2TDecodeSample { int topk; float topp; unsigned long long key; } S2TDecodeSample;
+int s2t_decode_step_sample(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, void* stream);
+int s2t_decode_graph_create_sample(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, int n_steps,
+                                   void** graph_exec);
 
 /* ---- measurement aid: what a collective costs the kernels beside it, on ONE GPU (bench.py data_parallel.dry_run) --------------------
  * `workgroups` workgroups stay resident on `stream` for the time a ring all-reduce of `bytes` over `ranks` ranks takes at `bus_gbps`
