@@ -16,14 +16,16 @@
 #include "common.hpp"
 #include "prof.hpp"
 #include "s2t_hip.h"
+#include "wgrad_plan.hpp"
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 namespace {
 constexpr int TM = 128, TN = 128, BT = 32, SA = 144;            // tile, tokens per stage, LDS row stride (floats)
+using wgrad_plan::ItemF;            // one 128 x 128 tile over stages [s0, s1) of 32 tokens (wgrad_plan.hpp, which builds the list)
+static_assert(wgrad_plan::TILE_F32 == TM && TM == TN && wgrad_plan::STAGE_F32 == BT && sizeof(ItemF) == 24, "the planner's tile and record are the kernel's");
 struct ProbF { const float *dY, *X; float *dW, *db; int n_out, n_in, tokens, ldy, ldx, ldw; };
-struct ItemF { int prob, tm, tn, s0, s1, atomic; };              // stages [s0, s1) of 32 tokens; atomic: a piece of a tile cut along the tokens
 
 __global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(const ProbF* __restrict__ probs, const ItemF* __restrict__ items, int n_items) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][A | B][BT][SA]
@@ -135,31 +137,11 @@ extern "C" int s2t_wgrad_group_f32(int n, const S2TWgradProblem* probs, void* st
         ProbF& p = pv[i];
         p.dY = (const float*)s.dY; p.X = (const float*)s.X; p.dW = s.dW; p.db = s.db;
         p.n_out = s.n_out; p.n_in = s.n_in; p.tokens = s.tokens; p.ldy = s.ldy; p.ldx = s.ldx; p.ldw = s.ldw;
-        for (int a = 0; a < (s.n_out + TM - 1) / TM; ++a)
-            for (int b = 0; b < (s.n_in + TN - 1) / TN; ++b) iv.push_back(ItemF{i, a, b, 0, (s.tokens + BT - 1) / BT, 0});
+        wgrad_plan::push_tiles_f32(iv, i, s.n_out, s.n_in, s.tokens);
         flops += 2.0 * s.n_out * (double)s.n_in * s.tokens;
         bytes += 4.0 * s.tokens * ((double)s.n_out + s.n_in) + 8.0 * s.n_out * (double)s.n_in;
     }
-    // longest reductions first, dealt round-robin to the workgroups: a launch takes as long as its most loaded workgroup
-    constexpr int SLOTS = 512;
-    auto len = [](const ItemF& t) { return t.s1 - t.s0; };
-    std::stable_sort(iv.begin(), iv.end(), [&](const ItemF& x, const ItemF& y) { return len(x) > len(y); });
-    {   // the long class = items at least half as long as the longest; its partly filled last round is cut to fill the round
-        size_t L = 0;
-        while (L < iv.size() && 2 * len(iv[L]) >= len(iv[0])) ++L;
-        const size_t rem = L % SLOTS;
-        if (L > SLOTS && rem > 0 && rem <= SLOTS / 2 && len(iv[0]) >= 16) {
-            const int f = (int)std::min<size_t>(8, SLOTS / rem);
-            std::vector<ItemF> cut;
-            for (size_t i = L - rem; i < L; ++i) {
-                const int n = len(iv[i]), per = (n + f - 1) / f;
-                for (int c = 0; c < n; c += per) cut.push_back(ItemF{iv[i].prob, iv[i].tm, iv[i].tn, c, std::min(n, c + per), 1});
-            }
-            iv.erase(iv.begin() + (L - rem), iv.begin() + L);
-            iv.insert(iv.end(), cut.begin(), cut.end());
-            std::stable_sort(iv.begin(), iv.end(), [&](const ItemF& x, const ItemF& y) { return len(x) > len(y); });
-        }
-    }
+    wgrad_plan::plan_f32(iv);           // longest reductions first, the long class's partly filled last round cut to fill it
     const size_t pb = pv.size() * sizeof(ProbF), ib = iv.size() * sizeof(ItemF);
     hipError_t se = hipSuccess;
     char* dev = (char*)s2t_scratch(S2T_SCRATCH_WGRAD_F32, st, pb + ib, &se);
@@ -174,7 +156,7 @@ extern "C" int s2t_wgrad_group_f32(int n, const S2TWgradProblem* probs, void* st
     const size_t lds = (size_t)2 * 2 * BT * SA * sizeof(float);
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    const int grid = (int)std::min<size_t>(iv.size(), SLOTS);
+    const int grid = wgrad_plan::grid_f32(iv.size());
     ProfScope prof("wgrad_group_f32", st, flops, bytes);
     hipLaunchKernelGGL(wgrad_f32_kernel, dim3(grid), dim3(256), lds, st, (const ProbF*)dev, (const ItemF*)(dev + pb), (int)iv.size());
     S2T_LAUNCH_CHECK();

@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "prof.hpp"
 #include "gemm_tile.hpp"
+#include "wgrad_plan.hpp"
 #include "../../include/s2t_hip.h"
 
 namespace {
@@ -25,9 +26,8 @@ struct Prob {
     const bf16* dY; const bf16* X; float* dW; float* db;
     int n_out, n_in, tokens, ldy, ldx, ldw, pad0, pad1;
 };
-// one work item = one 256 x 256 output tile over the K-tiles [kt0, kt1) of its problem.  `atomic`: the tile's token range is
-// shared with other items (a tile that straddles two workgroups' shares), so the result is ADDED with f32 atomics.
-struct Item { int prob, tm, tn, kt0, kt1, atomic; };
+using wgrad_plan::Item;             // one 256 x 256 output tile over K-tiles [kt0, kt1) of its problem (wgrad_plan.hpp, which builds the lists)
+static_assert(wgrad_plan::KTILE == BK && sizeof(Item) == 24, "the planner's K-tile and record are the kernel's");
 
 __device__ uint4 g_zero_page[64];                                  // 1 KiB of zeros (device globals are zero-initialised)
 }  // namespace
@@ -231,164 +231,13 @@ __global__ __launch_bounds__(512, 2) void wgrad_group_kernel(const Prob* __restr
     }
 }
 
-#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
-namespace {
-// ---- work lists.  A list is a table [round][slot]: workgroup slot s runs items s, s + G, s + 2G, ... until an empty one.
-// Cost model for comparing lists: an item costs its K-tiles plus C0 (pipeline fill from cold operands + the epilogue's 256 KB
-// read-modify-write, measured ~8 K-tile times at 40-K-tile items); a launch takes as long as its most loaded slot.
-constexpr int C0 = 8, MINP = 8;
-int G = 256;                      // workgroups of the launch = s2t_persistent_cus() when the list is built (under the entry point's mutex)
-struct Layout { std::vector<Item> table; int used = 0; long makespan = 0; };
-
-long load_of(const Layout& L) {
-    long worst = 0;
-    for (int sl = 0; sl < L.used; ++sl) {
-        long u = 0;
-        for (size_t it = sl; it < L.table.size(); it += L.used) {
-            const Item& t = L.table[it];
-            if (t.kt0 >= t.kt1) break;
-            u += t.kt1 - t.kt0 + C0;
-        }
-        worst = std::max(worst, u);
-    }
-    return worst;
-}
-
-// Layout 1 -- rounds.  Longest reductions first (stable: the tiles of one dW stay neighbours), dealt in rounds of one item per CU; the
-// workgroups of a round sweep the token range of neighbouring tiles in step, which is what lets the L2s / the MALL serve the
-// operand columns those tiles share (a schedule that balanced the CUs perfectly by handing each an arbitrary stretch of a line
-// of tiles ran 1.6x SLOWER: every tile then streams its 24 MB of operands from HBM alone).  Two cuts along the token range, whose
-// pieces meet in f32 atomics:
-//  * a tile whose reduction is much longer than a CU's fair share of the launch is cut into equal pieces of about that share, the
-//    same token ranges for all tiles of its dW;
-//  * a partly filled last round would leave CUs idle for a whole item's time: its items are cut into as many equal pieces as
-//    fill the round.
-// The right list for uniform groups (the encoder's 616 tiles of 375 K-tiles).
-void layout_rounds(std::vector<Item> iv, Layout& out) {
-    long units = 0;
-    for (const Item& t : iv) units += t.kt1 + 6;
-    const int share = (int)((units + G - 1) / G);
-    {
-        std::vector<Item> cutv;
-        cutv.reserve(iv.size());
-        for (size_t i = 0; i < iv.size();) {
-            size_t j = i;
-            while (j < iv.size() && iv[j].prob == iv[i].prob) ++j;           // the tiles of one dW: same reduction length
-            const int nk = iv[i].kt1;
-            const int f = nk > share + share / 4 ? std::min((nk + share - 1) / share, nk / MINP) : 1;
-            if (f <= 1) cutv.insert(cutv.end(), iv.begin() + i, iv.begin() + j);
-            else {
-                const int per = (nk + f - 1) / f;
-                for (int piece = 0; piece < f; ++piece)                      // piece-major: equal token ranges sit next to each other
-                    for (size_t k = i; k < j; ++k) {
-                        const int k0 = piece * per, k1 = std::min(nk, k0 + per);
-                        if (k0 < k1) cutv.push_back(Item{iv[k].prob, iv[k].tm, iv[k].tn, k0, k1, 1});
-                    }
-            }
-            i = j;
-        }
-        iv.swap(cutv);
-    }
-    std::stable_sort(iv.begin(), iv.end(), [](const Item& x, const Item& y) { return x.kt1 - x.kt0 > y.kt1 - y.kt0; });
-    const int rem = (int)(iv.size() % G);
-    if (rem) {
-        const int f = G / rem;
-        if (f >= 2) {
-            std::vector<Item> tail(iv.end() - rem, iv.end());
-            iv.resize(iv.size() - rem);
-            for (int piece = 0; piece < f; ++piece)
-                for (const Item& t : tail) {
-                    const int nk = t.kt1 - t.kt0, ff = std::max(1, std::min(f, nk / MINP)), per = (nk + ff - 1) / ff;
-                    const int k0 = t.kt0 + piece * per, k1 = std::min(t.kt1, k0 + per);
-                    if (piece < ff && k0 < k1) iv.push_back(Item{t.prob, t.tm, t.tn, k0, k1, ff > 1 ? 1 : t.atomic});
-                }
-        }
-    }
-    out.used = (int)std::min<size_t>(iv.size(), G);
-    out.table.swap(iv);
-    out.makespan = load_of(out);
-}
-
-// Layout 2 -- fill to a level.  For groups that mix a few very long reductions with many short ones (the decoder's: six K/V
-// projections over the ~24,000 source tokens = 48 tiles of 374 K-tiles next to 400 tiles of 40 K-tiles over its own 2,560 tokens):
-// the short tiles are dealt over the slots whole (1 or 2 each), then the long dWs are poured into what is left of every slot up to
-// a common level T: the tiles of one dW always as a gang on neighbouring slots with the SAME token range (they sweep it in step, first
-// thing in their slots), the range cut wherever a gang's slots are full.  Every slot ends within a few K-tiles of T.
-bool layout_fill(const std::vector<Item>& tiles, Layout& out) {
-    struct Line { size_t first, count; int nk; };
-    std::vector<Line> lines;
-    long units = 0;
-    for (size_t i = 0; i < tiles.size();) {
-        size_t j = i;
-        while (j < tiles.size() && tiles[j].prob == tiles[i].prob) ++j;
-        lines.push_back(Line{i, j - i, tiles[i].kt1});
-        units += (long)(j - i) * (tiles[i].kt1 + C0);
-        i = j;
-    }
-    const long fair = units / G;
-    std::vector<Line> longs;
-    std::vector<Item> shorts;
-    long long_k = 0;
-    for (const Line& l : lines) {
-        if (l.nk + C0 > fair && l.count <= (size_t)G / 2 && l.nk >= 4 * MINP) { longs.push_back(l); long_k += (long)l.count * l.nk; }
-        else shorts.insert(shorts.end(), tiles.begin() + l.first, tiles.begin() + l.first + l.count);
-    }
-    if (longs.empty()) return false;
-    std::stable_sort(shorts.begin(), shorts.end(), [](const Item& x, const Item& y) { return x.kt1 > y.kt1; });
-    std::vector<std::vector<Item>> tail(G), head(G);
-    std::vector<long> base(G, 0);
-    for (size_t i = 0; i < shorts.size(); ++i) { tail[i % G].push_back(shorts[i]); base[i % G] += shorts[i].kt1 + C0; }
-    long sum_base = 0;
-    for (long b : base) sum_base += b;
-    std::vector<long> ld;
-    long T = (sum_base + long_k + (long)G * C0 + G - 1) / G;
-    for (int attempt = 0; attempt < 64; ++attempt, T += std::max(1L, T / 64)) {
-        for (auto& h : head) h.clear();
-        ld = base;
-        size_t sl = 0;
-        bool ok = true;
-        for (const Line& l : longs) {
-            int k0 = 0;
-            while (k0 < l.nk && ok) {
-                if (sl + l.count > (size_t)G) { ok = false; break; }
-                long cap = T;
-                for (size_t j = 0; j < l.count; ++j) cap = std::min(cap, T - ld[sl + j] - C0);
-                int len = (int)std::min<long>(cap, l.nk - k0);
-                if (l.nk - k0 - len > 0 && l.nk - k0 - len < MINP) len = l.nk - k0 - MINP;     // never leave a remainder shorter than MINP
-                if (len < MINP) { sl += l.count; continue; }                                    // this gang is full
-                for (size_t j = 0; j < l.count; ++j) {
-                    const Item& t = tiles[l.first + j];
-                    head[sl + j].push_back(Item{t.prob, t.tm, t.tn, k0, k0 + len, len == l.nk ? 0 : 1});
-                    ld[sl + j] += len + C0;
-                }
-                k0 += len;
-            }
-            if (!ok) break;
-        }
-        if (!ok) continue;
-        size_t rounds = 0;
-        for (int i = 0; i < G; ++i) rounds = std::max(rounds, head[i].size() + tail[i].size());
-        out.table.assign(rounds * G, Item{0, 0, 0, 0, 0, 0});
-        for (int i = 0; i < G; ++i) {
-            size_t r = 0;
-            for (const Item& t : head[i]) out.table[(r++) * G + i] = t;
-            for (const Item& t : tail[i]) out.table[(r++) * G + i] = t;
-        }
-        out.used = G;
-        out.makespan = load_of(out);
-        return true;
-    }
-    return false;
-}
-}  // namespace
-
 extern "C" int s2t_wgrad_group(int n, const S2TWgradProblem* probs, void* stream) {
-    if (n <= 0) return S2T_OK;
-    if (!probs) return S2T_EINVAL;
+    if (n == 0) return S2T_OK;
+    if (n < 0 || !probs) return S2T_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     // A training loop hands over the same list update after update (same shapes, and the caching allocator returns the same activation
     // addresses), so the last few lists are kept: their work tables stay on the device (the two pageable-memory copies of an upload
@@ -399,6 +248,7 @@ extern "C" int s2t_wgrad_group(int n, const S2TWgradProblem* probs, void* stream
     static Cached cache[4];
     static unsigned long long tick = 0;
     static std::mutex mu;
+    static int G = 256;               // workgroups the cached lists were laid out for = s2t_persistent_cus() when they were built
     const size_t key_bytes = (size_t)n * sizeof(S2TWgradProblem);
     int device = 0;
     (void)hipGetDevice(&device);
@@ -429,16 +279,11 @@ extern "C" int s2t_wgrad_group(int n, const S2TWgradProblem* probs, void* stream
             Prob& p = pv[i];
             p.dY = (const bf16*)s.dY; p.X = (const bf16*)s.X; p.dW = s.dW; p.db = s.db;
             p.n_out = s.n_out; p.n_in = s.n_in; p.tokens = s.tokens; p.ldy = s.ldy; p.ldx = s.ldx; p.ldw = s.ldw; p.pad0 = p.pad1 = 0;
-            const int nk = (s.tokens + BK - 1) / BK, tn = (s.n_in + 255) / 256, tmn = (s.n_out + 255) / 256;
-            for (int a = 0; a < tmn; ++a)
-                for (int b = 0; b < tn; ++b) iv.push_back(Item{i, a, b, 0, nk, 0});
+            wgrad_plan::push_tiles(iv, i, s.n_out, s.n_in, s.tokens);
             flops += 2.0 * s.n_out * (double)s.n_in * s.tokens;
             bytes += 2.0 * s.tokens * ((double)s.n_out + s.n_in) + 8.0 * s.n_out * (double)s.n_in;
         }
-        Layout lay, alt;
-        const bool have_alt = layout_fill(iv, alt);
-        layout_rounds(std::move(iv), lay);
-        if (have_alt && alt.makespan < lay.makespan) std::swap(lay, alt);
+        const wgrad_plan::Layout lay = wgrad_plan::plan(std::move(iv), G);
         // device-side tables (problems, then items) in one buffer
         const size_t pb = pv.size() * sizeof(Prob), ib = lay.table.size() * sizeof(Item), need = pb + ib;
         std::vector<char> host(need);

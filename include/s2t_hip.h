@@ -119,7 +119,11 @@ size_t s2t_gemm_relu_mask_bytes(int M, int N, int K);
  * dW is owned by one workgroup for the whole token range: no split-K, no atomics
  * (when the tile count does not fill the last round of one tile per CU, the tiles of that round are cut along the token range and
  * meet in f32 atomics).  Requirements: ldy, ldx multiples of 8 elements and >= the column count rounded up to 8, 16-byte aligned
- * operand bases; a dW must not appear twice in one call.  `probs` is a HOST array (uploaded stream-ordered with the work list). */
+ * operand bases; a dW must not appear twice in one call.  `probs` is a HOST array (uploaded stream-ordered with the work list).
+ * Refused with S2T_EINVAL, before anything is uploaded or launched (no dW or db of the list is touched): a problem that misses these
+ * requirements, has a NULL dY, X or dW or a size below 1; n_out or n_in below 8 (one 16-byte chunk of bf16: such products go to
+ * s2t_linear_wgrad); an operand of 4 GiB or more (tokens * ld * 2 bytes: the kernel addresses operands by 32-bit byte offsets);
+ * a negative n or, with n > 0, a NULL `probs`.  n = 0 is S2T_OK and does nothing. */
 typedef struct S2TWgradProblem {
     const void* dY; const void* X; float* dW; float* db;
     int n_out, n_in, tokens, ldy, ldx, ldw;
@@ -127,8 +131,11 @@ typedef struct S2TWgradProblem {
 int s2t_wgrad_group(int n, const S2TWgradProblem* probs, void* stream);
 /* The same for f32 operands (the parity mode; csrc/wgrad_f32.hip): exact-f32 MFMA, every 128 x 128 tile of every dW owned by one workgroup
  * over all its tokens (no atomics: results do not depend on scheduling), all tiles of all products dealt to two workgroups per CU,
- * longest reductions first.  Requirements: ldy, ldx multiples of 4 elements and >= the column count rounded up to 4, 16-byte aligned
- * operand bases; a dW must not appear twice in one call. */
+ * longest reductions first (when the longest tiles do not fill their last round of 512 workgroups, the tiles of that round are cut along
+ * the token range and meet in f32 atomics).  Requirements: ldy, ldx multiples of 4 elements and >= the column count rounded up to 4,
+ * 16-byte aligned operand bases; a dW must not appear twice in one call.  Refusals as above, without the minimum width and the 4 GiB
+ * limit: S2T_EINVAL for a problem that misses the requirements, a NULL dY, X or dW, a size below 1, a negative n or a NULL `probs`
+ * with n > 0; n = 0 is S2T_OK. */
 int s2t_wgrad_group_f32(int n, const S2TWgradProblem* probs, void* stream);
 
 /* out[n] += sum_m X[m][n]  (bias gradients of every nn.Linear above; f32 atomics) */
