@@ -13,6 +13,17 @@
 // workgroup, which multiplies the weight slice it streams from L2 by a 16-row MFMA tile (rows >= beam are duplicates of the last row
 // and never stored).  Per-head / per-slice shares of the two output projections and of fc2 are written as f32 slabs and summed, in a
 // fixed order, by the NEXT phase's prologue together with residual and bias: deterministic, no atomics, no extra launch.
+//
+// Two options ride behind the s2t_decode_*_ex entry points in S2TDecodeExtras (the descriptor's size is pinned), both as template forms
+// that the plain search never instantiates into its launches, and neither adds a launch:
+//   attention records (one model): the LAST layer's encoder-attention launch also stores its f32 probabilities per head (REC form of
+//     dec_cross_kernel: they sit in LDS anyway), and the final LayerNorm launch, which is per sentence and runs before the step counter
+//     advances, averages the heads in a fixed order into attn_hist[t] -- the same share-and-sum pattern as above.  The host gathers a
+//     hypothesis' [Ts, len] attention from those records along its parent links after the search (decode.py walk_records_slots);
+//   --layernorm-embedding members: the rows of a decoder input are normalised where they are written, a wave per row (LNE forms of
+//     dec_begin_kernel and of dec_sent_kernel's next-input loop; embed_row_ln).
+// What stays with the step-by-step loop of sequence_generator.py: n-gram size 1, a prefix that holds EOS, a negative diversity strength,
+// 32-wide heads, ensembles of mixed dtypes, ensembles that return attention, and shapes outside desc_ok's limits.
 #include "common.hpp"
 #include "sample.hpp"
 #include "s2t_hip.h"
@@ -722,8 +733,18 @@ struct CrossArgs {
 // DD as in dec_self_kernel.  TP = Tsp / 128 when the sentence's encoder keys and values of this head fit in registers beside the weights
 // (Tsp <= 256: 2 TP position tiles of keys and Tsp / KS k-steps of one value column tile per wave): they are requested at the top of the
 // launch with the weights, so nothing is waited for after the LayerNorm.  TP = 0: requested where they are used.
-template <typename T, int DD, int TP>
-__global__ __launch_bounds__(NTHREADS) void dec_cross_kernel(CrossArgs a) {
+// REC (s2t_decode_step_ex with attn_part, the LAST layer's launch only; the plain form compiles none of it): the head's f32
+// probabilities of the rows < beam also go to attn_part[h][n0 + r][0 .. Tsp) -- the softmax leaves them in `sc` beside the T-rounded
+// p_s, and the block [beam][Tsp] is contiguous on both sides: 16-byte stores behind the barrier that follows the softmax anyway.
+// Padded keys and the columns Ts .. Tsp have the score -inf: their probability is exactly 0.  The per-sentence launch that follows
+// the last layer (dec_final_kernel) sums the heads.
+struct CrossRecArgs : CrossArgs { float* attn_part; };
+template <bool REC> struct CrossArgsOf { typedef CrossArgs type; };
+template <> struct CrossArgsOf<true> { typedef CrossRecArgs type; };
+__device__ __forceinline__ float* cross_rec(const CrossArgs&) { return nullptr; }
+__device__ __forceinline__ float* cross_rec(const CrossRecArgs& a) { return a.attn_part; }
+template <typename T, int DD, int TP, bool REC = false>
+__global__ __launch_bounds__(NTHREADS) void dec_cross_kernel(typename CrossArgsOf<REC>::type a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int PER = FR<T>::PER, KS = FR<T>::KS, KST = DH / KS;
     constexpr bool PRE = DD > 0, PKV = TP > 0;
@@ -820,8 +841,15 @@ __global__ __launch_bounds__(NTHREADS) void dec_cross_kernel(CrossArgs a) {
     }
     lds_barrier();
     DSTAMP(1, 3);
-    softmax_rows<sizeof(T) == 2>(sc, Tsp, R, Tsp, [&](int r, int p, float v) { p_s[(size_t)r * ldp + p] = from_f32<T>(v); });
+    softmax_rows<sizeof(T) == 2>(sc, Tsp, R, Tsp, [&](int r, int p, float v) {
+        p_s[(size_t)r * ldp + p] = from_f32<T>(v);
+        if constexpr (REC) sc[(size_t)r * Tsp + p] = v;            // the f32 value, in the place of the exponential this thread just read
+    });
     lds_barrier();
+    if constexpr (REC) {
+        float* dst = cross_rec(a) + ((size_t)h * N + n0) * Tsp;     // rows n0 .. n0 + R - 1 of head h: R * Tsp floats in a row
+        for (int i = tid; i < R * (Tsp / 4); i += NTHREADS) *reinterpret_cast<f32x4*>(dst + 4 * i) = *reinterpret_cast<const f32x4*>(sc + 4 * i);
+    }
     DSTAMP(1, 4);
     {   // o = P V: wave w owns 16 of the 64 value columns; V is read through its transposed, fragment-major copy
         const T* ap = p_s + (size_t)arow * ldp + PER * (lane >> 4);
@@ -902,12 +930,52 @@ __global__ __launch_bounds__(NTHREADS) void dec_ffn_kernel(FfnArgs a) {
 
 // ------------------------------------------------------------------------------------------------ final LayerNorm (rows to global)
 struct FinalArgs { Pro pro; int beam, N, D, max_len; const int* steps; void* xn; };
-template <typename T>
-__global__ __launch_bounds__(NTHREADS) void dec_final_kernel(FinalArgs a) {
+// REC (with the REC form of the last layer's dec_cross_kernel): the sentence's record of this step,
+// attn_hist[t][n0 + r][p] = (1 / heads) sum_h attn_part[h][n0 + r][p], p < Ts, heads in order (fixed: no atomics), written before the
+// per-sentence launch advances steps[s]; a sentence past its last step writes nothing.  The loads go out before the prologue's.
+struct FinalRecArgs : FinalArgs { int heads, Ts, Tsp; const float* attn_part; float* attn_hist; };
+template <bool REC> struct FinalArgsOf { typedef FinalArgs type; };
+template <> struct FinalArgsOf<true> { typedef FinalRecArgs type; };
+__device__ __forceinline__ void final_rec(const FinalArgs&, int, int, int) { }
+__device__ __forceinline__ void final_rec(const FinalRecArgs& a, int t, int n0, int tid) {
+    const size_t hs = (size_t)a.N * a.Tsp;
+    const float inv = 1.0f / (float)a.heads;
+    float* out = a.attn_hist + ((size_t)t * a.N + n0) * a.Ts;
+    const float* in = a.attn_part + (size_t)n0 * a.Tsp;
+    // four elements per thread and four heads per round (heads = 4, 8 or 16) requested together: the shares were written by other CUs,
+    // so every load is an L2 round trip, and what counts is how many of them are dependent (beam 5 x 250 frames x 8 heads: four rounds)
+    const int total = a.beam * a.Ts;
+    for (int i0 = tid; i0 < total; i0 += 4 * NTHREADS) {
+        const float* src[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = min(i0 + u * NTHREADS, total - 1), r = i / a.Ts;      // past the end: the last element again (never stored)
+            src[u] = in + (size_t)r * a.Tsp + (i - r * a.Ts);
+        }
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < a.heads; h += 4) {
+            float x[4][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) x[k][u] = src[u][(size_t)(h + k) * hs];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] += x[k][u];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u * NTHREADS < total) out[i0 + u * NTHREADS] = v[u] * inv;
+    }
+}
+template <typename T, bool REC = false>
+__global__ __launch_bounds__(NTHREADS) void dec_final_kernel(typename FinalArgsOf<REC>::type a) {
     __shared__ float red0[32];
     const int s = blockIdx.x, n0 = s * a.beam;
     const int t_raw = a.steps[s];
     DSTAMP(6, 0);
+    if constexpr (REC) { if (t_raw <= a.max_len) final_rec(a, t_raw, n0, (int)threadIdx.x); }
     dec_prologue<T, 16>(a.pro, true, a.N, a.D, n0, a.beam, reinterpret_cast<T*>(a.xn) + (size_t)n0 * a.D, a.D, red0,
                         [&]() { return t_raw <= a.max_len; });
     DSTAMP(6, 1);
@@ -1304,10 +1372,56 @@ struct SentEnsArgs : SentArgs { int n_more; SentMember more[ENS_MAX - 1]; };
 // DIV (diverse_groups > 1): the groups and the strength ride behind the arguments of the plain forms, whose layout stays as it is
 struct SentDivArgs : SentArgs { int div_groups; float div_strength; };
 struct SentEnsDivArgs : SentEnsArgs { int div_groups; float div_strength; };
-template <bool ENS, bool DIV = false> struct SentArgsOf { typedef SentArgs type; };
-template <> struct SentArgsOf<true, false> { typedef SentEnsArgs type; };
-template <> struct SentArgsOf<false, true> { typedef SentDivArgs type; };
-template <> struct SentArgsOf<true, true> { typedef SentEnsDivArgs type; };
+// LNE (s2t_decode_step_ex with a member's lne_g; always on the ENS argument forms, n_more = 0 for one model): member j's
+// decoder.layernorm_embedding, or NULL for a member without one, behind the arguments of the plain forms
+template <typename Base> struct WithLne : Base { const float* lne_g[ENS_MAX]; const float* lne_b[ENS_MAX]; float lne_eps[ENS_MAX]; };
+template <bool ENS, bool DIV = false, bool LNE = false> struct SentArgsOf { typedef SentArgs type; };
+template <> struct SentArgsOf<true, false, false> { typedef SentEnsArgs type; };
+template <> struct SentArgsOf<false, true, false> { typedef SentDivArgs type; };
+template <> struct SentArgsOf<true, true, false> { typedef SentEnsDivArgs type; };
+template <> struct SentArgsOf<true, false, true> { typedef WithLne<SentEnsArgs> type; };
+template <> struct SentArgsOf<true, true, true> { typedef WithLne<SentEnsDivArgs> type; };
+// One row of a decoder input by ONE wave (all 64 lanes active): v = scale * e + pe (transformer.py:720-737), and with g set its
+// LayerNorm over D (transformer.py:731-732; fairseq/modules/layer_norm.py: biased variance, eps inside the root, f32 statistics) --
+// a lane holds D / 256 float4 of the row (D = 256, 512 or 1024), the two statistics are one DPP reduction each.
+template <typename T>
+__device__ __forceinline__ void embed_row_ln(const T* e, const float* pe, float scale, const float* g, const float* b, float eps, int D, float* out) {
+    const int lane = threadIdx.x & 63, nc = D >> 8;
+    f32x4 v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int col = (min(c, nc - 1) * 64 + lane) * 4;          // past the row: its last piece again (never stored)
+        const f32x4 ev = Raw4<T>::cvt(Raw4<T>::ld(e + col)), pv = *reinterpret_cast<const f32x4*>(pe + col);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[c][q] = scale * ev[q] + pv[q];
+    }
+    if (g) {
+        f32x4 gg[4], bb[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int col = (min(c, nc - 1) * 64 + lane) * 4;
+            gg[c] = *reinterpret_cast<const f32x4*>(g + col); bb[c] = *reinterpret_cast<const f32x4*>(b + col);
+        }
+        float sm = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sm += c < nc ? (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]) : 0.f;
+        const float mean = group_sum<64>(sm) / (float)D;
+        float q2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const f32x4 d = v[c] - mean;
+            q2 += c < nc ? (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]) : 0.f;
+        }
+        const float rstd = rsqrtf(group_sum<64>(q2) / (float)D + eps);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[c][q] = (v[c][q] - mean) * rstd * gg[c][q] + bb[c][q];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < nc) *reinterpret_cast<f32x4*>(out + (c * 64 + lane) * 4) = v[c];
+}
 // an entry's value under the Hamming penalty of group-diverse beam search: v - strength * count, the product and the difference each
 // rounded to f32 (tests/decode_diverse_ref.py restates it bit for bit); -inf stays -inf.  The empty asm keeps the product a value of
 // its own: the device build contracts a * b - c into one fused multiply-add otherwise, through __fmul_rn / __fsub_rn and the fp
@@ -1336,9 +1450,10 @@ __device__ __forceinline__ SentMember ens_member(const SentEnsArgs& a, int j) {
 // SAMPLE (the sampling search, with the SAMPLE form of the row launch): exactly `beam` candidates, candidate r = the one entry slot r's
 // row launch wrote, its parent slot r (slot 0 at step 0: search.py:269-272); everything behind the forming of the candidates is the
 // code of the beam search run with k = beam.
-template <typename T, bool ENS = false, bool DIV = false, bool SAMPLE = false>
-__global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<ENS, DIV>::type a) {
+template <typename T, bool ENS = false, bool DIV = false, bool SAMPLE = false, bool LNE = false>
+__global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<ENS, DIV, LNE>::type a) {
     static_assert(!(DIV && SAMPLE), "a sampling search has no groups");
+    static_assert(!LNE || ENS, "the LayerNorm form rides on the ensemble arguments");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ __attribute__((aligned(16))) float l_val[16 * 32];
     __shared__ __attribute__((aligned(16))) int l_idx[16 * 32];
@@ -1470,6 +1585,17 @@ __global__ __launch_bounds__(NTHREADS) void dec_sent_kernel(typename SentArgsOf<
         // ENS: the same for every member, member 0 (SentArgs' own fields) first
         for (int mj = 0; mj < (ENS ? 1 + ens_more(a) : 1); ++mj) {
             const SentMember me = ens_member(a, mj);
+            if constexpr (LNE) {
+                // a wave per row (rows w, w + 4, ...): the row's LayerNorm statistics stay inside the wave
+                const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+                for (int j = w; j < beam; j += NTHREADS / 64) {
+                    const int tok = pick_tok[j];
+                    embed_row_ln<T>(reinterpret_cast<const T*>(me.embed) + (size_t)tok * me.D,
+                                    me.pos_table + (size_t)(tok == a.pad ? a.pad : a.pad + 2 + t) * me.D, me.embed_scale, a.lne_g[mj], a.lne_b[mj],
+                                    a.lne_eps[mj], me.D, me.x0 + (size_t)(n0 + j) * me.D);
+                }
+                continue;
+            }
             const int dq = me.D / 4, items = beam * dq;
             for (int i0 = 0; i0 < items; i0 += 4 * NTHREADS) {
                 f32x4 ev4[4], pv4[4];
@@ -1506,13 +1632,24 @@ struct BeginArgs {
     int beam, N, D, pad, bos; float embed_scale;
     int* steps; int* tok_hist; int* blacklist; int* nfin; int* finished; const void* embed; const float* pos_table; float* x0;
 };
-template <typename T>
-__global__ __launch_bounds__(NTHREADS) void dec_begin_kernel(BeginArgs a) {
+// LNE (s2t_decode_begin_ex with the member's lne_g): the <bos> rows through decoder.layernorm_embedding, a wave per row
+struct BeginLneArgs : BeginArgs { const float *lne_g, *lne_b; float lne_eps; };
+template <bool LNE> struct BeginArgsOf { typedef BeginArgs type; };
+template <> struct BeginArgsOf<true> { typedef BeginLneArgs type; };
+template <typename T> __device__ __forceinline__ bool begin_lne(const BeginLneArgs& a, const T* e, const float* pe, int n0) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    for (int j = w; j < a.beam; j += NTHREADS / 64)
+        embed_row_ln<T>(e, pe, a.embed_scale, a.lne_g, a.lne_b, a.lne_eps, a.D, a.x0 + (size_t)(n0 + j) * a.D);
+    return true;
+}
+template <typename T, bool LNE = false>
+__global__ __launch_bounds__(NTHREADS) void dec_begin_kernel(typename BeginArgsOf<LNE>::type a) {
     const int s = blockIdx.x, tid = threadIdx.x, n0 = s * a.beam;
     if (tid == 0) { a.steps[s] = 0; a.nfin[s] = 0; a.finished[s] = 0; }
     if (tid < a.beam) { a.blacklist[n0 + tid] = 0; a.tok_hist[n0 + tid] = a.bos; }
     const T* e = reinterpret_cast<const T*>(a.embed) + (size_t)a.bos * a.D;
     const float* pe = a.pos_table + (size_t)(a.bos == a.pad ? a.pad : a.pad + 1) * a.D;
+    if constexpr (LNE) { begin_lne<T>(a, e, pe, n0); return; }
     for (int j = 0; j < a.beam; ++j)
         for (int d = tid; d < a.D; d += NTHREADS) a.x0[(size_t)(n0 + j) * a.D + d] = a.embed_scale * to_f32(e[d]) + pe[d];
 }
@@ -1603,6 +1740,7 @@ template <typename T, int DD> hipError_t configure_dd() {
     DEC_ALLOW((dec_self_kernel<T, 4, DD>)); DEC_ALLOW((dec_self_kernel<T, 5, DD>)); DEC_ALLOW((dec_self_kernel<T, 6, DD>));
     DEC_ALLOW((dec_self_kernel<T, 7, DD>)); DEC_ALLOW((dec_self_kernel<T, 8, DD>)); DEC_ALLOW((dec_self_kernel<T, 16, DD>));
     DEC_ALLOW((dec_cross_kernel<T, DD, 0>)); DEC_ALLOW((dec_cross_kernel<T, DD, 1>)); DEC_ALLOW((dec_cross_kernel<T, DD, 2>));
+    DEC_ALLOW((dec_cross_kernel<T, DD, 0, true>)); DEC_ALLOW((dec_cross_kernel<T, DD, 1, true>)); DEC_ALLOW((dec_cross_kernel<T, DD, 2, true>));
     DEC_ALLOW((dec_ffn_kernel<T, 1, DD>)); DEC_ALLOW((dec_ffn_kernel<T, 2, DD>)); DEC_ALLOW((dec_ffn_kernel<T, 4, DD>));
     return hipSuccess;
 }
@@ -1616,6 +1754,8 @@ template <typename T> hipError_t configure() {
     DEC_ALLOW(dec_sent_kernel<T>); DEC_ALLOW((dec_sent_kernel<T, true>));
     DEC_ALLOW((dec_sent_kernel<T, false, true>)); DEC_ALLOW((dec_sent_kernel<T, true, true>));
     DEC_ALLOW((dec_sent_kernel<T, false, false, true>)); DEC_ALLOW((dec_sent_kernel<T, true, false, true>));
+    DEC_ALLOW((dec_sent_kernel<T, true, false, false, true>)); DEC_ALLOW((dec_sent_kernel<T, true, true, false, true>));
+    DEC_ALLOW((dec_sent_kernel<T, true, false, true, true>));
     DEC_ALLOW((dec_logits_kernel<T, 1>)); DEC_ALLOW((dec_logits_kernel<T, 2>)); DEC_ALLOW((dec_logits_kernel<T, 3>)); DEC_ALLOW((dec_logits_kernel<T, 4>));
     DEC_ALLOW((dec_logits_kernel<T, 5>)); DEC_ALLOW((dec_logits_kernel<T, 6>)); DEC_ALLOW((dec_logits_kernel<T, 7>)); DEC_ALLOW((dec_logits_kernel<T, 8>));
     return hipSuccess;
@@ -1638,6 +1778,12 @@ void launch_cross(int tp, dim3 grid, size_t lds, hipStream_t st, const CrossArgs
     else hipLaunchKernelGGL((dec_cross_kernel<T, DD, 0>), grid, dim3(NTHREADS), lds, st, a);
 }
 template <typename T, int DD>
+void launch_cross_rec(int tp, dim3 grid, size_t lds, hipStream_t st, const CrossRecArgs& a) {
+    if (tp == 1) hipLaunchKernelGGL((dec_cross_kernel<T, DD, 1, true>), grid, dim3(NTHREADS), lds, st, a);
+    else if (tp == 2) hipLaunchKernelGGL((dec_cross_kernel<T, DD, 2, true>), grid, dim3(NTHREADS), lds, st, a);
+    else hipLaunchKernelGGL((dec_cross_kernel<T, DD, 0, true>), grid, dim3(NTHREADS), lds, st, a);
+}
+template <typename T, int DD>
 void launch_ffn(int hs, dim3 grid, size_t lds, hipStream_t st, const FfnArgs& a) {
     if (hs == 64) hipLaunchKernelGGL((dec_ffn_kernel<T, 1, DD>), grid, dim3(NTHREADS), lds, st, a);
     else if (hs == 128) hipLaunchKernelGGL((dec_ffn_kernel<T, 2, DD>), grid, dim3(NTHREADS), lds, st, a);
@@ -1649,8 +1795,10 @@ namespace {
 constexpr int DEC_STOPPED = 1;           // chain_impl: the decode_stop_after diagnostic ended the step
 #define DEC_STOP_CHECK() do { if (g_s2t_opt_decode_stop_after > 0 && ++launched >= g_s2t_opt_decode_stop_after) { S2T_LAUNCH_CHECK(); return DEC_STOPPED; } } while (0)
 // one model's launches up to its logits (3 * layers + 2); `launched` counts for decode_stop_after, across the members of an ensemble
+// rec_part / rec_hist (S2TDecodeExtras attn_part / attn_hist, or both NULL): the last layer's C launch and the final LayerNorm in
+// their recording forms; every other launch, and every launch without them, is the one it always was
 template <typename T>
-int chain_impl(const S2TDecodeDesc* d, hipStream_t st, int& launched) {
+int chain_impl(const S2TDecodeDesc* d, hipStream_t st, int& launched, float* rec_part = nullptr, float* rec_hist = nullptr) {
     const int B = d->B, R = d->beam, N = B * R, D = d->D, H = d->heads, FS = d->ffn_slices, hs = d->ffn / FS, maxpos = d->max_len + 1;
     const LdsNeed need = lds_need(d);
     float* X[2] = {d->x0, d->x1};
@@ -1681,7 +1829,15 @@ int chain_impl(const S2TDecodeDesc* d, hipStream_t st, int& launched) {
             a.max_len = d->max_len; a.scale = scale; a.w_q = y.w_xq; a.b_q = (const float*)y.b_xq; a.w_o = y.w_xo; a.kv_enc = y.kv_enc;
             a.vt_enc = y.vt_enc; a.klen = d->enc_klen; a.steps = d->steps; a.part_out = P[k & 1];
             const int tp = d->Tsp == 128 ? 1 : (d->Tsp == 256 ? 2 : 0);     // encoder keys / values in registers for the launch
-            if (dd == 256) launch_cross<T, (sizeof(T) == 2 ? 256 : 0)>(tp, dim3(H, B), need.cross, st, a);
+            if (rec_part && l == d->layers - 1) {
+                CrossRecArgs ra;
+                static_cast<CrossArgs&>(ra) = a;
+                ra.attn_part = rec_part;
+                if (dd == 256) launch_cross_rec<T, (sizeof(T) == 2 ? 256 : 0)>(tp, dim3(H, B), need.cross, st, ra);
+                else if (dd == 512) launch_cross_rec<T, (sizeof(T) == 2 ? 512 : 0)>(tp, dim3(H, B), need.cross, st, ra);
+                else launch_cross_rec<T, 0>(tp, dim3(H, B), need.cross, st, ra);
+            }
+            else if (dd == 256) launch_cross<T, (sizeof(T) == 2 ? 256 : 0)>(tp, dim3(H, B), need.cross, st, a);
             else if (dd == 512) launch_cross<T, (sizeof(T) == 2 ? 512 : 0)>(tp, dim3(H, B), need.cross, st, a);
             else launch_cross<T, 0>(tp, dim3(H, B), need.cross, st, a);
             ++k; np = H; bias = (const float*)y.b_xo;
@@ -1698,8 +1854,10 @@ int chain_impl(const S2TDecodeDesc* d, hipStream_t st, int& launched) {
         }
     }
     {
-        FinalArgs a; a.pro = pro(d->lnf_g, d->lnf_b); a.beam = R; a.N = N; a.D = D; a.max_len = d->max_len; a.steps = d->steps; a.xn = d->xn;
-        hipLaunchKernelGGL(dec_final_kernel<T>, dim3(B), dim3(NTHREADS), 0, st, a);
+        FinalRecArgs a; a.pro = pro(d->lnf_g, d->lnf_b); a.beam = R; a.N = N; a.D = D; a.max_len = d->max_len; a.steps = d->steps; a.xn = d->xn;
+        a.heads = H; a.Ts = d->Ts; a.Tsp = d->Tsp; a.attn_part = rec_part; a.attn_hist = rec_hist;
+        if (rec_part) hipLaunchKernelGGL((dec_final_kernel<T, true>), dim3(B), dim3(NTHREADS), 0, st, a);
+        else hipLaunchKernelGGL(dec_final_kernel<T>, dim3(B), dim3(NTHREADS), 0, st, static_cast<const FinalArgs&>(a));
         DEC_STOP_CHECK();
     }
     {
@@ -1739,13 +1897,44 @@ void sent_args(const S2TDecodeDesc* d, SentArgs& a) {
         else if (vpt <= 24) DEC_ROW(24); else if (vpt <= 32) DEC_ROW(32); else if (vpt <= 40) DEC_ROW(40); else if (vpt <= 48) DEC_ROW(48); \
         else if (vpt <= 64) DEC_ROW(64); else if (vpt <= 96) DEC_ROW(96); else DEC_ROW(128); } while (0)
 // r: the rules of s2t_decode_step_rules, or NULL (checked by rules_check); smp: the sampling search of s2t_decode_step_sample, or NULL
+// the per-sentence launch in its LNE form (x names a member's layernorm_embedding): the ensemble arguments, n - 1 further members
 template <typename T>
-int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st) {
+void launch_sent_lne(const S2TDecodeDesc* const* dv, int n, const S2TDecodeSample* smp, const S2TDecodeExtras* x, hipStream_t st) {
+    const S2TDecodeDesc* d = dv[0];
+    WithLne<SentEnsDivArgs> a;
+    sent_args(d, a);
+    a.div_groups = d->diverse_groups; a.div_strength = d->diverse_strength;
+    a.n_more = n - 1;
+    for (int j = 1; j < ENS_MAX; ++j) {
+        SentMember& o = a.more[j - 1];
+        if (j < n) { o.embed = dv[j]->embed; o.pos_table = dv[j]->pos_table; o.x0 = dv[j]->x0; o.D = dv[j]->D; o.embed_scale = dv[j]->embed_scale; }
+        else { o.embed = nullptr; o.pos_table = nullptr; o.x0 = nullptr; o.D = 0; o.embed_scale = 0.f; }
+    }
+    for (int j = 0; j < ENS_MAX; ++j) {
+        a.lne_g[j] = j < n ? x->lne_g[j] : nullptr; a.lne_b[j] = j < n ? x->lne_b[j] : nullptr; a.lne_eps[j] = j < n ? dv[j]->ln_eps : 0.f;
+    }
+    const dim3 grid(d->B), block(NTHREADS);
+    const size_t lds = lds_need(d).sent;
+    if (smp || d->diverse_groups <= 1) {
+        WithLne<SentEnsArgs> b;                                   // the form without the groups: the fields of `a` but the two
+        static_cast<SentEnsArgs&>(b) = static_cast<const SentEnsArgs&>(a);
+        for (int j = 0; j < ENS_MAX; ++j) { b.lne_g[j] = a.lne_g[j]; b.lne_b[j] = a.lne_b[j]; b.lne_eps[j] = a.lne_eps[j]; }
+        if (smp) hipLaunchKernelGGL((dec_sent_kernel<T, true, false, true, true>), grid, block, lds, st, b);
+        else hipLaunchKernelGGL((dec_sent_kernel<T, true, false, false, true>), grid, block, lds, st, b);
+    } else hipLaunchKernelGGL((dec_sent_kernel<T, true, true, false, true>), grid, block, lds, st, a);
+}
+inline bool has_lne(const S2TDecodeExtras* x, int n) {
+    if (x) for (int j = 0; j < n; ++j) if (x->lne_g[j]) return true;
+    return false;
+}
+template <typename T>
+int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st, const S2TDecodeExtras* x = nullptr) {
     int launched = 0;
-    const int rc = chain_impl<T>(d, st, launched);
+    const int rc = chain_impl<T>(d, st, launched, x ? x->attn_part : nullptr, x ? x->attn_hist : nullptr);
     if (rc != S2T_OK) return rc == DEC_STOPPED ? S2T_OK : rc;
     const int B = d->B, N = B * d->beam;
     const LdsNeed need = lds_need(d);
+    const bool lne = has_lne(x, 1);
     if (smp) {
         RowRuleSampleArgs a;
         row_args(d, r, r && (r->no_repeat_ngram > 0 || r->prefix_len > 0), a);
@@ -1753,9 +1942,12 @@ int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, const S2TDecodeSa
 #define DEC_ROW(VPT_) hipLaunchKernelGGL((dec_row_kernel<VPT_, true, false, true>), dim3(N), dim3(NTHREADS), 0, st, a)
         DEC_ROW_BY_VPT(d->V);
 #undef DEC_ROW
-        SentArgs b;
-        sent_args(d, b);
-        hipLaunchKernelGGL((dec_sent_kernel<T, false, false, true>), dim3(B), dim3(NTHREADS), need.sent, st, b);
+        if (lne) launch_sent_lne<T>(&d, 1, smp, x, st);
+        else {
+            SentArgs b;
+            sent_args(d, b);
+            hipLaunchKernelGGL((dec_sent_kernel<T, false, false, true>), dim3(B), dim3(NTHREADS), need.sent, st, b);
+        }
         S2T_LAUNCH_CHECK();
         return S2T_OK;
     }
@@ -1768,7 +1960,8 @@ int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, const S2TDecodeSa
         DEC_ROW_BY_VPT(d->V);
 #undef DEC_ROW
     }
-    {
+    if (lne) launch_sent_lne<T>(&d, 1, nullptr, x, st);
+    else {
         SentDivArgs a;
         sent_args(d, a);
         a.div_groups = d->diverse_groups; a.div_strength = d->diverse_strength;
@@ -1783,7 +1976,8 @@ int step_impl(const S2TDecodeDesc* d, const S2TDecodeRules* r, const S2TDecodeSa
 // buffers, one after the other on `st`, then ONE row launch over all the members' logits and ONE sentence launch that also writes every
 // member's next input.  The serial order is what makes the shared `steps` and `anc` safe: no member's chain runs beside the sentence launch.
 template <typename T>
-int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st) {
+int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st,
+                  const S2TDecodeExtras* x = nullptr) {
     int launched = 0;
     for (int j = 0; j < n; ++j) {
         const int rc = chain_impl<T>(dv[j], st, launched);
@@ -1808,7 +2002,8 @@ int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r
 #undef DEC_ROW
         }
     }
-    {
+    if (has_lne(x, n)) launch_sent_lne<T>(dv, n, smp, x, st);
+    else {
         SentEnsDivArgs a;
         sent_args(d, a);
         a.div_groups = d->diverse_groups; a.div_strength = d->diverse_strength;
@@ -1827,17 +2022,19 @@ int step_ens_impl(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r
 }
 
 template <typename T>
-int begin_impl(const S2TDecodeDesc* d, int bos, hipStream_t st) {
+int begin_impl(const S2TDecodeDesc* d, int bos, hipStream_t st, const float* lne_g = nullptr, const float* lne_b = nullptr) {
     static bool configured = false;                         // per instantiation: raises the dynamic-LDS limit of the step's kernels once
     if (!configured) {
         const hipError_t e = configure<T>();
         if (e != hipSuccess) return S2T_EHIP(e);
         configured = true;
     }
-    BeginArgs a; a.beam = d->beam; a.N = d->B * d->beam; a.D = d->D; a.pad = d->pad; a.bos = bos; a.embed_scale = d->embed_scale; a.steps = d->steps;
+    BeginLneArgs a; a.lne_g = lne_g; a.lne_b = lne_b; a.lne_eps = d->ln_eps;
+    a.beam = d->beam; a.N = d->B * d->beam; a.D = d->D; a.pad = d->pad; a.bos = bos; a.embed_scale = d->embed_scale; a.steps = d->steps;
     a.tok_hist = d->tok_hist; a.blacklist = d->blacklist; a.nfin = d->nfin; a.finished = d->finished; a.embed = d->embed; a.pos_table = d->pos_table;
     a.x0 = d->x0;
-    hipLaunchKernelGGL(dec_begin_kernel<T>, dim3(d->B), dim3(NTHREADS), 0, st, a);
+    if (lne_g) hipLaunchKernelGGL((dec_begin_kernel<T, true>), dim3(d->B), dim3(NTHREADS), 0, st, a);
+    else hipLaunchKernelGGL(dec_begin_kernel<T>, dim3(d->B), dim3(NTHREADS), 0, st, static_cast<const BeginArgs&>(a));
     S2T_LAUNCH_CHECK();
     return S2T_OK;
 }
@@ -1929,8 +2126,9 @@ static int ensemble_check(const S2TDecodeDesc* const* dv, int n, const S2TDecode
     return S2T_OK;
 }
 template <typename T>
-static int step_any(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st) {
-    return n == 1 ? step_impl<T>(dv[0], r, smp, st) : step_ens_impl<T>(dv, n, r, smp, st);
+static int step_any(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, hipStream_t st,
+                    const S2TDecodeExtras* x = nullptr) {
+    return n == 1 ? step_impl<T>(dv[0], r, smp, st, x) : step_ens_impl<T>(dv, n, r, smp, st, x);
 }
 
 extern "C" int s2t_decode_begin_ensemble(const S2TDecodeDesc* const* dv, int n, int bos, void* stream) {
@@ -1988,7 +2186,8 @@ extern "C" int s2t_decode_pack_weight(int dtype, const void* W, int ldw, int N, 
 }
 
 // n_steps x step_any(dv, n, r, smp) recorded on a private stream as one chain and instantiated; the arguments are checked by the callers
-static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, int n_steps, void** graph_exec) {
+static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* smp, int n_steps, void** graph_exec,
+                        const S2TDecodeExtras* x = nullptr) {
     hipStream_t cs = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
     if (e != hipSuccess) return S2T_EHIP(e);
@@ -1997,7 +2196,7 @@ static int graph_record(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRu
     int out = S2T_OK;
     e = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed);
     if (e == hipSuccess) {
-        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, smp, cs) : step_any<float>(dv, n, r, smp, cs);
+        for (int i = 0; i < n_steps && out == S2T_OK; ++i) out = dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, smp, cs, x) : step_any<float>(dv, n, r, smp, cs, x);
         e = hipStreamEndCapture(cs, &g);
     }
     if (e == hipSuccess && out == S2T_OK) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
@@ -2032,6 +2231,41 @@ extern "C" int s2t_decode_graph_create_sample(const S2TDecodeDesc* const* dv, in
     const int rc = sample_check(dv, n, r, s);
     if (rc != S2T_OK) return rc;
     return graph_record(dv, n, r, s, n_steps, graph_exec);
+}
+// the checks of the *_ex calls, in the order include/s2t_hip.h documents
+static int extras_check(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, const S2TDecodeExtras* x) {
+    if (x) {
+        if ((x->attn_part == nullptr) != (x->attn_hist == nullptr)) return S2T_EINVAL;
+        for (int j = 0; j < ENS_MAX; ++j) if ((x->lne_g[j] == nullptr) != (x->lne_b[j] == nullptr)) return S2T_EINVAL;
+        if (x->attn_part && n > 1) return S2T_ENOTSUP;
+    }
+    return s ? sample_check(dv, n, r, s) : ensemble_check(dv, n, r);
+}
+extern "C" int s2t_decode_begin_ex(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, const S2TDecodeExtras* x,
+                                   int bos, void* stream) {
+    const int rc = extras_check(dv, n, r, s, x);
+    if (rc != S2T_OK) return rc;
+    if (bos < 0 || bos >= dv[0]->V) return S2T_EINVAL;
+    for (int j = 0; j < n; ++j) {
+        const float *g = x ? x->lne_g[j] : nullptr, *b = x ? x->lne_b[j] : nullptr;
+        const int rj = dv[j]->dtype == S2T_BF16 ? begin_impl<bf16>(dv[j], bos, (hipStream_t)stream, g, b) : begin_impl<float>(dv[j], bos, (hipStream_t)stream, g, b);
+        if (rj != S2T_OK) return rj;
+    }
+    return S2T_OK;
+}
+extern "C" int s2t_decode_step_ex(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, const S2TDecodeExtras* x,
+                                  void* stream) {
+    const int rc = extras_check(dv, n, r, s, x);
+    if (rc != S2T_OK) return rc;
+    return dv[0]->dtype == S2T_BF16 ? step_any<bf16>(dv, n, r, s, (hipStream_t)stream, x) : step_any<float>(dv, n, r, s, (hipStream_t)stream, x);
+}
+extern "C" int s2t_decode_graph_create_ex(const S2TDecodeDesc* const* dv, int n, const S2TDecodeRules* r, const S2TDecodeSample* s,
+                                          const S2TDecodeExtras* x, int n_steps, void** graph_exec) {
+    if (!graph_exec || n_steps < 1 || n_steps > 64) return S2T_EINVAL;
+    *graph_exec = nullptr;
+    const int rc = extras_check(dv, n, r, s, x);
+    if (rc != S2T_OK) return rc;
+    return graph_record(dv, n, r, s, n_steps, graph_exec, x);
 }
 extern "C" int s2t_decode_graph_create(const S2TDecodeDesc* d, int n_steps, void** graph_exec) {
     return s2t_decode_graph_create_rules(d, nullptr, n_steps, graph_exec);

@@ -15,8 +15,12 @@ score rules and one sentence launch does the bookkeeping and embeds the chosen t
 `SequenceGenerator` (sequence_generator.py) takes this path for one model or an ensemble with the plain, the hierarchical or the
 group-diverse beam search (`diverse_groups`: the per-sentence launch forms the groups' penalised candidates from the same row lists), with n-gram blocking (n >= 2) and prefix tokens (without EOS) as two more score rules of the per-row launch
 (`s2t_decode_step_rules`), or with the sampling search (`sampling`: each row draws its one candidate inside the per-row launch,
-`s2t_decode_step_sample`), and keeps its step-by-step path (the same decoder kernels + torch index bookkeeping) for attention output,
-a prefix that holds EOS, n-gram size 1, members of different dtypes and any member outside the shape limits.
+`s2t_decode_step_sample`).  Two options ride in `S2TDecodeExtras` behind the `s2t_decode_*_ex` calls: `--layernorm-embedding` members
+(the rows of every decoder input are normalised where they are written) and, for one model, `retain_attention`: the last layer's
+encoder-attention launch also stores its per-head probabilities, the final LayerNorm launch averages them into one record per step,
+and `hypotheses` gathers every hypothesis' `[Ts, len]` attention from those records along its parent links.  The generator keeps its
+step-by-step path (the same decoder kernels + torch index bookkeeping) for an ensemble that returns attention, a prefix that holds
+EOS, n-gram size 1, members of different dtypes and any member outside the shape limits.
 """
 import ctypes
 import math
@@ -27,6 +31,7 @@ import torch
 
 from . import lib as L
 
+ATTN_HIST_CAP = 1 << 30              # bytes of attention records ((max_len + 1) * N * Ts * 4) a session accepts: beyond, `ok` is False
 POLL_STEPS = 8                       # the host reads the `finished` flags every POLL_STEPS steps (one small D2H copy + sync)
 LDS_CAP = 152 * 1024                 # csrc/decode.hip LDS_CAP
 
@@ -136,10 +141,15 @@ class EnsembleDecodeSession:
     sampling: None, or dict(topk, topp, key) -- the sampling search (fairseq/search.py:164-278; the draw of include/s2t_hip.h
     S2TDecodeSample): forms of the per-row and per-sentence launches behind s2t_decode_step_sample / s2t_decode_graph_create_sample;
     not with diverse_groups > 1 nor step0_all_slots.  None launches exactly what was launched before.
+    retain_attention (one member only; `ok` False otherwise, or when the records would pass ATTN_HIST_CAP): every hypothesis of
+    `hypotheses` carries `attention`, f32 [Ts, len], the last layer's encoder attention averaged over its heads.  A member whose
+    engine has `hp.layernorm_embedding` gets its decoder inputs normalised.  With neither, the session goes through the entry points
+    it always used; with either, through s2t_decode_begin_ex / _step_ex / _graph_create_ex (S2TDecodeExtras).
     The other arguments as BeamDecodeSession's."""
 
     def __init__(self, members, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0, init_scores=None,
-                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0, diverse_strength=0.5, sampling=None):
+                 step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0, diverse_strength=0.5, sampling=None,
+                 retain_attention=False):
         members = list(members)
         assert members, "an ensemble needs at least one member"
         engine, enc_out = members[0][0], members[0][2]
@@ -163,6 +173,11 @@ class EnsembleDecodeSession:
             sm = self.sample = L.DecodeSample()
             sm.topk, sm.topp, sm.key = max(topk, 0), topp, int(sampling.get("key", 0)) & 0xFFFFFFFFFFFFFFFF
             self.sample_addr = ctypes.addressof(sm)
+        self.extras, self.extras_addr, self.attn_hist, self.attn_part = None, None, None, None
+        self.retain_attention = bool(retain_attention)
+        lne = [bool(getattr(m[0].hp, "layernorm_embedding", False)) for m in members]
+        if self.retain_attention and (len(members) != 1 or (max_len + 1) * N * enc_out.shape[0] * 4 > ATTN_HIST_CAP):
+            self.ok = False                                             # (include/s2t_hip.h: S2TDecodeExtras; the cap is this module's)
         if not self.ok:
             return
         sh = dict(beam=beam, max_len=max_len, min_len=min_len, pad=pad, unk=unk, eos=eos, V=V, unk_penalty=unk_penalty, temperature=temperature,
@@ -216,6 +231,19 @@ class EnsembleDecodeSession:
         for mem in self.members:
             mem.fill()
         self.bufs_of = [mem.bufs for mem in self.members]
+        if self.retain_attention or any(lne):
+            x = self.extras = L.DecodeExtras()
+            for j, mem in enumerate(self.members):
+                if lne[j]:
+                    g, b = mem.engine.P(mem.pfx + "layernorm_embedding.weight"), mem.engine.P(mem.pfx + "layernorm_embedding.bias")
+                    keep += [g, b]
+                    x.lne_g[j], x.lne_b[j] = g.data_ptr(), b.data_ptr()
+            if self.retain_attention:
+                d0 = self.members[0].desc
+                self.attn_part = torch.empty((d0.heads, N, d0.Tsp), dtype=torch.float32, device=dev)
+                self.attn_hist = torch.empty((max_len + 1, N, d0.Ts), dtype=torch.float32, device=dev)
+                x.attn_part, x.attn_hist = self.attn_part.data_ptr(), self.attn_hist.data_ptr()
+            self.extras_addr = ctypes.addressof(x)
         n = len(self.members)
         self.desc_array = (ctypes.c_void_p * n)(*[mem.addr for mem in self.members])     # the HOST array of descriptors of the *_ensemble calls
         self.descs_addr = ctypes.addressof(self.desc_array)
@@ -237,13 +265,19 @@ class EnsembleDecodeSession:
         st = L.stream()
         n = len(self.members)
         one = self.members[0].addr if n == 1 else None      # one model: the one-model entry points, as ever
-        if one:
+        xa = self.extras_addr                               # an option of S2TDecodeExtras: the *_ex entry points for everything
+        if xa:
+            L.check(lib.s2t_decode_begin_ex(self.descs_addr, n, self.rules_addr, self.sample_addr, xa, int(bos), st), "s2t_decode_begin_ex")
+        elif one:
             L.check(lib.s2t_decode_begin(one, int(bos), st), "s2t_decode_begin")
         else:
             L.check(lib.s2t_decode_begin_ensemble(self.descs_addr, n, int(bos), st), "s2t_decode_begin_ensemble")
         exec_ = ctypes.c_void_p(0)
         per = POLL_STEPS if graph else 1                    # steps per launch: one recorded graph holds POLL_STEPS of them
-        if graph and self.sample_addr:
+        if graph and xa:
+            L.check(lib.s2t_decode_graph_create_ex(self.descs_addr, n, self.rules_addr, self.sample_addr, xa, per, ctypes.addressof(exec_)),
+                    "s2t_decode_graph_create_ex")
+        elif graph and self.sample_addr:
             L.check(lib.s2t_decode_graph_create_sample(self.descs_addr, n, self.rules_addr, self.sample_addr, per, ctypes.addressof(exec_)),
                     "s2t_decode_graph_create_sample")
         elif graph and not one:
@@ -260,6 +294,8 @@ class EnsembleDecodeSession:
             while steps < self.max_len + 1:
                 if graph:
                     L.check(lib.s2t_decode_graph_launch(exec_.value, st), "s2t_decode_graph_launch")
+                elif xa:
+                    L.check(lib.s2t_decode_step_ex(self.descs_addr, n, self.rules_addr, self.sample_addr, xa, st), "s2t_decode_step_ex")
                 elif self.sample_addr:
                     L.check(lib.s2t_decode_step_sample(self.descs_addr, n, self.rules_addr, self.sample_addr, st), "s2t_decode_step_sample")
                 elif not one:
@@ -288,7 +324,7 @@ class EnsembleDecodeSession:
         iv = lambda k: ib[self.ioff[k][0]:self.ioff[k][0] + self.ioff[k][1]]
         fv = lambda k: fb[self.foff[k][0]:self.foff[k][0] + self.foff[k][1]]
         M2 = self.max_len + 2
-        sent, tok, pos, score, origin, length = walk_records(
+        sent, tok, pos, score, origin, length, slots = walk_records_slots(
             iv("tok_hist").reshape(M2, N), iv("par_hist").reshape(M2, N), fv("cum_hist").reshape(M2, N), iv("nfin"),
             iv("fin_step").reshape(B, beam), iv("fin_row").reshape(B, beam), fv("fin_score").reshape(B, beam), beam, self.pad, self.eos,
             normalize_scores, len_penalty)
@@ -299,6 +335,16 @@ class EnsembleDecodeSession:
             n = int(length[f])
             out[int(sent[f])].append({"tokens": tok_d[f, :n], "score": score_d[f], "attention": None, "alignment": None,
                                       "positional_scores": pos_d[f, :n], "origin": int(origin[f]), "_score": float(score[f])})
+        if self.attn_hist is not None and sent.shape[0]:
+            # position p of a hypothesis was produced by step p on slot slots[f, p] of arrangement p: one gather of the records
+            # (index work only, as finalize_hypos' index_select on the step route); columns past a hypothesis' length are cut off
+            slots_d = torch.from_numpy(slots).to(dev)
+            rec = self.attn_hist[torch.arange(slots.shape[1], device=dev)[None, :], slots_d]        # [F, Lmax, Ts]
+            count = [0] * B
+            for f in range(sent.shape[0]):
+                s = int(sent[f])
+                out[s][count[s]]["attention"] = rec[f, :int(length[f])].t()                        # src_len x tgt_len (:510-514)
+                count[s] += 1
         return out
 
 
@@ -307,14 +353,16 @@ class BeamDecodeSession(EnsembleDecodeSession):
     no_repeat_ngram_size: 0 (off) or >= 2 (1 is refused: `ok` False); prefix_tokens: integer [B, P], pad = free, WITHOUT EOS (the
     caller checks: sequence_generator._device_search) -- the session keeps its int32 device copy alive for the recorded graph.
     The one-member form of EnsembleDecodeSession: `desc`, `addr` and `bufs` are the member's, and `run` goes through the one-model
-    entry points (s2t_decode_begin, s2t_decode_step[_rules], s2t_decode_graph_create[_rules])."""
+    entry points (s2t_decode_begin, s2t_decode_step[_rules], s2t_decode_graph_create[_rules]), or, with retain_attention or a
+    --layernorm-embedding engine, through the *_ex ones."""
 
     def __init__(self, engine, pfx, enc_out, enc_klen, beam, max_len, min_len, pad, unk, eos, V, unk_penalty=0.0, temperature=1.0,
                  init_scores=None, step0_all_slots=False, no_repeat_ngram_size=0, prefix_tokens=None, diverse_groups=0,
-                 diverse_strength=0.5, sampling=None):
+                 diverse_strength=0.5, sampling=None, retain_attention=False):
         super().__init__([(engine, pfx, enc_out, enc_klen)], beam, max_len, min_len, pad, unk, eos, V, unk_penalty, temperature,
                          init_scores=init_scores, step0_all_slots=step0_all_slots, no_repeat_ngram_size=no_repeat_ngram_size,
-                         prefix_tokens=prefix_tokens, diverse_groups=diverse_groups, diverse_strength=diverse_strength, sampling=sampling)
+                         prefix_tokens=prefix_tokens, diverse_groups=diverse_groups, diverse_strength=diverse_strength, sampling=sampling,
+                         retain_attention=retain_attention)
         if self.members:
             m = self.members[0]
             self.desc, self.addr, self.layers = m.desc, m.addr, m.layers
@@ -323,12 +371,20 @@ class BeamDecodeSession(EnsembleDecodeSession):
 
 
 def walk_records(tok_h, par_h, cum_h, nfin, fin_step, fin_row, fin_score, beam, pad, eos, normalize_scores, len_penalty):
+    """walk_records_slots without the slots"""
+    return walk_records_slots(tok_h, par_h, cum_h, nfin, fin_step, fin_row, fin_score, beam, pad, eos, normalize_scores, len_penalty)[:6]
+
+
+def walk_records_slots(tok_h, par_h, cum_h, nfin, fin_step, fin_row, fin_score, beam, pad, eos, normalize_scores, len_penalty):
     """Host side of the device search (numpy): from the per-step selection records -- arrangement i = the beam after i selections:
     tok_h[i][n] the token slot n received, par_h[i][n] the slot of arrangement i-1 it continues, cum_h[i][n] its cumulative score --
     and the finalisation records (step, parent slot, score of the EOS candidate; nfin[s] of them per sentence, in the order the
     reference appends them) to what finalize_hypos builds (sequence_generator.py:502-560): tokens (ending in EOS), positional scores
     (differences of the cumulative ones), the length-normalised score (:553-554) and the step-0 slot each hypothesis descends from.
-    Returns (sentence, tokens [F, Lmax] pad-filled, positional scores, score, origin, length), one row per hypothesis."""
+    Returns (sentence, tokens [F, Lmax] pad-filled, positional scores, score, origin, length, slots), one row per hypothesis.
+    slots [F, Lmax] (0 past the length): slots[f, p] = the slot of arrangement p the hypothesis occupied when step p produced its
+    token at target position p -- the final EOS comes from `fin_row` at `fin_step`, the earlier ones along `par_h` -- i.e. where the
+    per-step records of that step (attn_hist[p]) hold what belongs to it."""
     B = nfin.shape[0]
     sel = np.arange(beam)[None, :] < nfin[:, None]
     sent = np.nonzero(sel)[0]
@@ -340,19 +396,22 @@ def walk_records(tok_h, par_h, cum_h, nfin, fin_step, fin_row, fin_score, beam, 
     tok = np.full((F, Tm + 1), pad, dtype=np.int64)
     cum = np.zeros((F, Tm + 1), dtype=np.float32)
     idx = np.arange(F)
+    slots = np.zeros((F, Tm + 1), dtype=np.int64)
     tok[idx, fstep] = eos
     cum[idx, fstep] = fsc
+    slots[idx, fstep] = rows
     for i in range(Tm, 0, -1):                                         # arrangement i -> i-1 along the parent links
         act = fstep >= i
         r = rows[act]
         tok[act, i - 1] = tok_h[i][r]
         cum[act, i - 1] = cum_h[i][r]
         rows[act] = par_h[i][r]
+        slots[act, i - 1] = rows[act]
     origin = rows % beam
     pos = cum.copy()
     pos[:, 1:] = cum[:, 1:] - cum[:, :-1]
     score = fsc / ((fstep + 1).astype(np.float64) ** len_penalty).astype(np.float32) if normalize_scores else fsc
-    return sent, tok, pos, score.astype(np.float32), origin, fstep + 1
+    return sent, tok, pos, score.astype(np.float32), origin, fstep + 1, slots
 
 
 def device_search_enabled():

@@ -112,6 +112,9 @@ SIGNATURES = {
     "s2t_decode_graph_create_ensemble": [P, c_int, P, c_int, P],
     "s2t_decode_step_sample": [P, c_int, P, P, P],
     "s2t_decode_graph_create_sample": [P, c_int, P, P, c_int, P],
+    "s2t_decode_begin_ex": [P, c_int, P, P, P, c_int, P],
+    "s2t_decode_step_ex": [P, c_int, P, P, P, P],
+    "s2t_decode_graph_create_ex": [P, c_int, P, P, P, c_int, P],
     "s2t_sample_rows": [P, c_long, c_int, c_int, c_int, c_int, c_float, c_ull, c_int, P, P, P, P],
     "s2t_decode_graph_launch": [P, P],
     "s2t_decode_graph_destroy": [P],
@@ -176,6 +179,11 @@ class DecodeRules(ctypes.Structure):
 class DecodeSample(ctypes.Structure):
     """S2TDecodeSample of include/s2t_hip.h"""
     _fields_ = [("topk", c_int), ("topp", c_float), ("key", c_ull)]
+
+
+class DecodeExtras(ctypes.Structure):
+    """S2TDecodeExtras of include/s2t_hip.h"""
+    _fields_ = [("lne_g", c_void_p * 8), ("lne_b", c_void_p * 8), ("attn_part", c_void_p), ("attn_hist", c_void_p)]
 
 
 _lib = None

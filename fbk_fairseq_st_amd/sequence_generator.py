@@ -16,10 +16,12 @@ Ensembles (EnsembleModel.forward_decoder :711-770: every member runs its own enc
 log-probabilities meet in one logsumexp kernel), prefix tokens (:270-280,449-476) and n-gram blocking (:617-650) follow the
 reference.  The search of one model or of an ensemble of up to eight runs device-resident (decode.py), n-gram blocking with n >= 2 and prefix
 tokens without EOS included: both are score rules of its per-row kernel, which for an ensemble also takes the log of the members' mean
-probability.  The step-by-step loop below serves `retain_attention`, `--layernorm-embedding`, n-gram size 1, a prefix that holds EOS,
+probability.  `--layernorm-embedding` models and one model's `retain_attention` run there too (decode.py: S2TDecodeExtras).  The
+step-by-step loop below serves ensembles with `retain_attention`, n-gram size 1, a prefix that holds EOS,
 ensembles whose members differ in compute dtype or hold a member outside the device route's shape limits (and S2T_DEVICE_SEARCH=0); with `retain_attention=True` every hypothesis carries its `attention` (src_len x tgt_len, the last decoder layer's
-encoder-attention averaged over heads and ensemble members: sequence_generator.py:286-292,510-560,757-768) and, with `print_alignment`, the
-hard `alignment` generate.py prints (utils.extract_hard_alignment, fairseq/utils.py).
+encoder-attention averaged over heads and ensemble members: sequence_generator.py:286-292,510-560,757-768; on the device route gathered
+from its per-step records after the loop) and, with `print_alignment`, the hard `alignment` generate.py prints
+(utils.extract_hard_alignment, fairseq/utils.py), on either route.
 The sampling search (`Sampling`, fairseq/search.py:164-278: unrestricted, top-k, nucleus) runs device-resident as well -- forms of the
 per-row and per-sentence launches that draw one token per row with a stateless Gumbel-max draw -- and through `kernels.sample_rows` on
 the step-by-step loop, which serves a hierarchical start besides the cases above.
@@ -186,8 +188,8 @@ class SequenceGenerator:
             raise NotImplementedError("match_source_len / retain_dropout are outside the S2T hot path")
         self.no_repeat_ngram_size = int(no_repeat_ngram_size)
         # the reference records the averaged encoder attention of every step whenever the decoder returns one (:286-292); here it costs
-        # a kernel per step (the fused attention never materialises P), so it is on request -- task.build_generator sets it for
-        # generate.py --print-alignment
+        # a kernel per step on the step-by-step route (the fused attention never materialises P) and a store per head on the device
+        # route, so it is on request -- task.build_generator sets it for generate.py --print-alignment
         self.print_alignment = bool(print_alignment)
         self.retain_attention = bool(retain_attention) or self.print_alignment
         self.search = BeamSearch(tgt_dict) if search_strategy is None else search_strategy
@@ -256,7 +258,8 @@ class SequenceGenerator:
         members' mean probability), with n-gram blocking and prefix tokens as score rules of the per-row launch; None when this search
         needs the step-by-step path below: n-gram size 1 (the reference then bans EOS through the <bos> column), a prefix that holds
         EOS (the reference then copies slot 0 over the sentence's other slots, :449-476), members of different compute dtypes, or a
-        shape the session refuses for any member."""
+        shape the session refuses for any member.  `retain_attention` (one decoder: _beam_search keeps ensembles away) and
+        `--layernorm-embedding` members are options of the session."""
         from . import decode as DEC
         if not DEC.device_search_enabled() or type(search) not in (BeamSearch, HierarchicalBeamSearch, DiverseBeamSearch, Sampling):
             return None
@@ -276,8 +279,6 @@ class SequenceGenerator:
         if ngram == 1:
             return None
         engs = [d.engine for d in decoders]
-        if any(e.hp.layernorm_embedding for e in engs):                    # the step's first launch takes the embedding sum as it is
-            return None
         eos_ = [e.encoder_out.contiguous() for e in encs]
         if not all(eo.is_cuda for eo in eos_):   # host tensors only reach this class under the CPU tests' stand-in engine (tests/cpu_stubs.py: host logic)
             return None
@@ -291,7 +292,7 @@ class SequenceGenerator:
         if len(decoders) == 1:
             ses = DEC.BeamDecodeSession(engs[0], decoders[0].pfx, eos_[0], klens[0], self.beam_size, max_len, self.min_len, pad, unk, eos, V,
                                         self.unk_penalty, self.temperature, init_scores=prev_scores, step0_all_slots=prev_scores is not None,
-                                        no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens, **div)
+                                        no_repeat_ngram_size=ngram, prefix_tokens=prefix_tokens, retain_attention=self.retain_attention, **div)
         else:
             ses = DEC.EnsembleDecodeSession([(g, d.pfx, eo, kl) for g, d, eo, kl in zip(engs, decoders, eos_, klens)], self.beam_size, max_len,
                                             self.min_len, pad, unk, eos, V, self.unk_penalty, self.temperature, init_scores=prev_scores,
@@ -318,7 +319,8 @@ class SequenceGenerator:
         beam = self.beam_size
         decoders = list(decoder) if isinstance(decoder, (list, tuple)) else [decoder]
         encs = list(enc) if isinstance(decoder, (list, tuple)) else [enc]
-        if 1 <= len(decoders) <= 8 and not self.retain_attention and all(d.owner.training is False for d in decoders):
+        # an ensemble that returns attention averages it over its members: the step-by-step loop's work
+        if 1 <= len(decoders) <= 8 and (not self.retain_attention or len(decoders) == 1) and all(d.owner.training is False for d in decoders):
             out = self._device_search(decoders, encs, B, max_len, search, bos_token, pad, unk, eos, V, prev_scores, prefix_tokens)
             if out is not None:
                 return out

@@ -562,6 +562,37 @@ int s2t_decode_step_sample(const S2TDecodeDesc* const* d, int n, const S2TDecode
 int s2t_decode_graph_create_sample(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, int n_steps,
                                    void** graph_exec);
 
+/* ---- two options of the device-resident search that S2TDecodeDesc (whose size is pinned) has no room for ----------------------------
+ * S2TDecodeExtras is HOST memory read during the call only; the pointers in it are DEVICE memory that must stay where it is while a
+ * graph recorded with it is replayed.
+ *   lne_g[j], lne_b[j]  f32 [D_j]: member j's decoder.layernorm_embedding (--layernorm-embedding, fairseq/models/transformer.py:731-732),
+ *                       or both NULL for a member without one.  Every row of a decoder input, embed_scale * embed[token] + position, is
+ *                       normalised over D in f32 (biased variance, the member's ln_eps inside the root) before it is stored to x0: the
+ *                       <bos> rows by begin, the next step's rows by the per-sentence launch (a wave per row).
+ *   attn_part           f32 [heads][N][Tsp]: scratch for the per-head probabilities (one model only).
+ *   attn_hist           f32 [max_len + 1][N][Ts]: record t, slot n = the encoder-attention probabilities of the LAST decoder layer,
+ *                       averaged over the heads (fixed order, x 1 / heads), of the hypothesis that occupied slot n when step t ran, i.e.
+ *                       BEFORE that step's selection (fairseq/sequence_generator.py:286-292 with alignment_layer's default); keys at or
+ *                       beyond enc_klen[s] are exactly 0.  A sentence past its last step writes nothing.  Both NULL: nothing is recorded.
+ * The last layer's C launch also stores its f32 probabilities to attn_part, and the final LayerNorm launch (per sentence) sums the heads
+ * into attn_hist before the per-sentence launch advances steps[s]: the number of launches does not change, and every other launch is the
+ * one the calls below make without `x`.
+ * The three calls generalise begin / step / graph_create of every form above: n = 1..8 members, r the rules or NULL, s the sampling search
+ * or NULL.  x == NULL, or every field of it NULL: exactly the launches of s2t_decode_begin_ensemble / s2t_decode_step_ensemble (s == NULL)
+ * or s2t_decode_step_sample (s != NULL) and their graph_create (n == 1: those of the one-model calls).  Checked before any launch, in
+ * this order (graph_create: graph_exec and n_steps first, S2T_EINVAL, *graph_exec left NULL on every failure): with x != NULL, one of
+ * attn_part / attn_hist without the other, or one of lne_g[j] / lne_b[j] without the other for any j < 8 -> S2T_EINVAL; attn_part with
+ * n > 1 -> S2T_ENOTSUP (an ensemble's attention stays with the caller); then, s != NULL: everything s2t_decode_step_sample checks, in its
+ * order; s == NULL: everything s2t_decode_step_ensemble checks, in its order; begin_ex then bos as s2t_decode_begin.  Entries lne_g[j],
+ * j >= n, are not looked at beyond the pairing check. */
+typedef struct S2TDecodeExtras { const float* lne_g[8]; const float* lne_b[8]; float* attn_part; float* attn_hist; } S2TDecodeExtras;
+int s2t_decode_begin_ex(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, const S2TDecodeExtras* x,
+                        int bos, void* stream);
+int s2t_decode_step_ex(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, const S2TDecodeSample* s, const S2TDecodeExtras* x,
+                       void* stream);
+int s2t_decode_graph_create_ex(const S2TDecodeDesc* const* d, int n, const S2TDecodeRules* r, const S2TDecodeSample* s,
+                               const S2TDecodeExtras* x, int n_steps, void** graph_exec);
+
 /* ---- measurement aid: what a collective costs the kernels beside it, on ONE GPU (bench.py data_parallel.dry_run) --------------------
  * `workgroups` workgroups stay resident on `stream` for the time a ring all-reduce of `bytes` over `ranks` ranks takes at `bus_gbps`
  * (2 (ranks - 1) / ranks * bytes / bus) and copy src -> dst twice meanwhile, evenly paced.  Stands in for RCCL's kernels of
