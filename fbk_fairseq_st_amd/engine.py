@@ -218,6 +218,11 @@ class S2TEngine:
         # diagnostic: a dict here collects the ReLU decisions of the next forward passes of the per-kernel (f32) schedule, site ->
         # bool tensor (tests/test_configs_gpu.py hands them to the oracle, so that the fp32 comparison holds no discrete decision)
         self.relu_record = None
+        # diagnostic: a dict here collects what the next FORWARD passes did at every dropout site with p > 0, site -> (p, seed, shape of
+        # the index space the launch hashed: attention sites (B, heads, Tq, Tk), whose rows the kernels pitch at (Tk + 3) & ~3).  Only
+        # forward code writes it and nothing reads it: tests/test_dropout_parity_gpu.py rebuilds every mask from it for the oracle, so
+        # the backward's own seed arithmetic is checked against something it did not produce.
+        self.dropout_record = None
         # True: the decoder's queued weight gradients go out at the end of ITS backward (data-parallel runs: ~130 MB of gradients
         # then travel under the encoder's backward).  False: they wait for the encoder's flush and share its launch; measured on one GPU
         # (tools/ab_engine_flag.py flush_decoder_wgrad): 15.63 ms per update against 15.48 with the separate launch -- the one work
@@ -313,6 +318,10 @@ class S2TEngine:
     def G(self, n):
         return self.A.g(n)
 
+    def _drop_rec(self, site, p, seed, shape):
+        if self.dropout_record is not None and p > 0:
+            self.dropout_record[site] = (float(p), int(seed), tuple(int(v) for v in shape))
+
     def linear(self, x2d, name, act=K.ACT_NONE, residual=None, aux_out=None, p_drop=0.0, seed=0, bias=True, pad_rows=False):
         w = self.W(name + ".weight")
         out = K.alloc_rows((x2d.shape[0],), w.shape[0], self.dtype, self.dev) if pad_rows else None
@@ -354,6 +363,7 @@ class S2TEngine:
                                                bufs["encoder.bn.0.running_mean"], bufs["encoder.bn.0.running_var"],
                                                bufs["encoder.bn.0.num_batches_tracked"], cnt1, training, hp.bn_momentum, hp.bn_eps)
         y1n = K.bn_apply(y1, sc1, sh1, p_sub, seed + 1)
+        self._drop_rec("encoder.conv0.drop", p_sub, seed + 1, (B, T2, F2, C))
         # conv2 as implicit GEMM + BN2
         w2p = K.permute_conv_w(self.P("encoder.convolutions.1.weight"), torch.empty((C, 9 * C), dtype=self.dtype, device=self.dev), C, C, 0)
         P2 = T4 * B * F4
@@ -369,6 +379,7 @@ class S2TEngine:
                                                bufs["encoder.bn.1.running_mean"], bufs["encoder.bn.1.running_var"],
                                                bufs["encoder.bn.1.num_batches_tracked"], P2, training, hp.bn_momentum, hp.bn_eps)
         z2n = K.bn_apply(z2, sc2, sh2, p_sub, seed + 2)
+        self._drop_rec("encoder.conv1.drop", p_sub, seed + 2, (T4, B, F4, C))
         a2d = []
         if hp.attn_2d:                           # x = x + ConvAttention2D(x), twice (conv_transformer.py:216-222)
             for i in range(2):
@@ -390,6 +401,7 @@ class S2TEngine:
         else:
             xe = K.add_pos(h3.view(T4, B, hp.D), self.table(T4 + 1, 0), len4_32, out=torch.empty((T4, B, hp.D), dtype=self.dtype, device=self.dev),
                            p_drop=p, seed=seed + 3)
+        self._drop_rec("encoder.embed.drop", p, seed + 3, (T4, B, hp.D))
         if self.relu_record is not None and not gelu:           # reference layouts: (B,C,T2,F2), (B,C,T4,F4), (T4,B,D)
             self.relu_record["encoder.conv0"] = (y1.view(B, T2, F2, C) > 0).permute(0, 3, 1, 2)
             self.relu_record["encoder.conv1"] = (z2.view(T4, B, F4, C) > 0).permute(1, 3, 0, 2)
@@ -587,6 +599,8 @@ class S2TEngine:
                               p_drop=pa, seed=seed + 1, dist_penalty=dist_penalty)
         p = hp.dropout if training else 0.0
         y = self.linear(ctx.view(T * B, D), pfx + "self_attn.out_proj", residual=x2, p_drop=p, seed=seed + 2)
+        self._drop_rec(pfx + "self_attn.probs", pa, seed + 1, (B, hp.heads, T, T))
+        self._drop_rec(pfx + "self_attn.out", p, seed + 2, (T, B, D))
         c = dict(x=x2, h=h, mean=mean, rstd=rstd, qkv=qkv, ctx=ctx, lse=lse, klen=klen32, causal=causal, pa=pa, p=p, seed=seed, T=T, B=B,
                  dist_penalty=dist_penalty)
         return y.view(T, B, D), c
@@ -621,6 +635,8 @@ class S2TEngine:
         ctx, lse = K.attn_fwd(q, kv[:, :, :D], kv[:, :, D:], hp.heads, klen=enc_klen32, causal=False, p_drop=pa, seed=seed + 1)
         p = hp.dropout if training else 0.0
         y = self.linear(ctx.view(T * B, D), pfx + "encoder_attn.out_proj", residual=x2, p_drop=p, seed=seed + 2)
+        self._drop_rec(pfx + "encoder_attn.probs", pa, seed + 1, (B, hp.heads, T, Ts))
+        self._drop_rec(pfx + "encoder_attn.out", p, seed + 2, (T, B, D))
         c = dict(x=x2, h=h, mean=mean, rstd=rstd, q=q, kv=kv, ctx=ctx, lse=lse, klen=enc_klen32, pa=pa, p=p, seed=seed, T=T, B=B, Ts=Ts, enc2d=enc2d)
         return y.view(T, B, D), c
 
@@ -657,7 +673,9 @@ class S2TEngine:
                         p_drop=pact, seed=seed + 3)
         p = hp.dropout if training else 0.0
         y = self.linear(a, pfx + "fc2", residual=x2, p_drop=p, seed=seed + 4)
-        if self.relu_record is not None and hp.act == "relu" and pact == 0.0:
+        self._drop_rec(pfx + "ffn.act", pact, seed + 3, (T, B, hp.ffn))
+        self._drop_rec(pfx + "ffn.out", p, seed + 4, (T, B, D))
+        if self.relu_record is not None and hp.act == "relu":       # with activation dropout: a > 0 <=> active AND kept
             self.relu_record[pfx + "ffn"] = (a > 0).view(T, B, hp.ffn)
         c = dict(x=x2, h=h, mean=mean, rstd=rstd, a=a, pre=pre, pact=pact, p=p, seed=seed, amask=amask)
         return y.view(T, B, D), c
@@ -736,6 +754,15 @@ class S2TEngine:
         c.x = x.data_ptr(); c.enc = enc2d.data_ptr() if decoder else None; c.y = y.data_ptr(); c.ws = ws.data_ptr()
         K.layer_fwd(e["addr"], ctypes.addressof(c))
         p = self.hp.dropout if training else 0.0
+        if self.dropout_record is not None and training:          # the rates csrc/layer.hip reads from the descriptor, its six seeds
+            hp = self.hp
+            self._drop_rec(pfx + "self_attn.probs", hp.attention_dropout, seeds[0], (B, hp.heads, T, T))
+            self._drop_rec(pfx + "self_attn.out", p, seeds[1], (T, B, D))
+            if decoder:
+                self._drop_rec(pfx + "encoder_attn.probs", hp.attention_dropout, seeds[2], (B, hp.heads, T, Ts))
+                self._drop_rec(pfx + "encoder_attn.out", p, seeds[3], (T, B, D))
+            self._drop_rec(pfx + "ffn.act", hp.activation_dropout, seeds[4], (T, B, hp.ffn))
+            self._drop_rec(pfx + "ffn.out", p, seeds[5], (T, B, D))
         return y, dict(composite=True, pfx=pfx, decoder=decoder, shape=shape, ntmp=ntmp, ws=ws, x=x, enc2d=enc2d, self_klen=self_klen,
                        enc_klen=enc_klen, seeds=seeds, training=training, p=p, T=T, B=B, Ts=Ts)
 
@@ -923,6 +950,7 @@ class S2TEngine:
             x = xn.view(L, B, D)
         if p > 0:
             K.dropout(x, p, seed * 1000 + 501, out=x)
+        self._drop_rec(pfx + "embed.drop", p, seed * 1000 + 501, (L, B, D))
         tlen = tok.ne(hp.pad).sum(dim=1).to(torch.int32)            # integer bookkeeping (suffix padding)
         Ts = enc_out.shape[0]
         enc2d = enc_out.reshape(Ts * B, D)

@@ -40,6 +40,40 @@ def site_act(cfg, site, act):
     return lambda x: x * m.reshape(x.shape).to(x.dtype)
 
 
+def site_drop(cfg, site, x):
+    """The dropout of one site.  With no entry for the site it is the identity (parity mode: every golden fixture without masks).
+    With cfg["drop_masks"][site] = (keep, p) -- checker-only, keep a bool tensor in this function's layout -- it is F.dropout's
+    arithmetic with the KEEP DECISIONS taken from the caller: y = x * keep / (1 - p).  The parity tests feed it the masks the
+    product drew (rebuilt from what its forward recorded), the way `site_act` feeds the ReLU active sets; the reference fixture
+    (tests/golden/dropout.npz) feeds it the masks a patched F.dropout drew inside the real reference, which pins every site's
+    PLACE: the calls below stand exactly where the reference calls F.dropout."""
+    m = (cfg.get("drop_masks") or {}).get(site)
+    if m is None:
+        return x
+    keep, p = m
+    return x * keep.reshape(x.shape).to(x.dtype) / (1 - p)
+
+
+def _probs_drop(cfg, site):
+    """keyword of `mha` for the mask on its probabilities -- passed only when the site has one, so that a call without masks is the
+    call it always was"""
+    m = (cfg.get("drop_masks") or {}).get(site)
+    return {} if m is None else {"drop": m}
+
+
+def drop_sites(cfg, decoder="decoder."):
+    """Names of the dropout sites in the order the reference's forward calls F.dropout (encoder, then decoder)."""
+    s = ["encoder.conv0.drop", "encoder.conv1.drop", "encoder.embed.drop"]
+    for l in range(cfg["enc_layers"]):
+        p = "encoder.layers.%d." % l
+        s += [p + "self_attn.probs", p + "self_attn.out", p + "ffn.act", p + "ffn.out"]
+    s.append(decoder + "embed.drop")
+    for l in range(cfg["dec_layers"]):
+        p = decoder + "layers.%d." % l
+        s += [p + "self_attn.probs", p + "self_attn.out", p + "encoder_attn.probs", p + "encoder_attn.out", p + "ffn.act", p + "ffn.out"]
+    return s
+
+
 def act_fn(name):
     # fairseq/utils.py:390-408 ; fairseq/modules/gelu.py:24-25 (gelu in fp32)
     if name == "relu":
@@ -140,7 +174,7 @@ def conv_attention_2d(W, p, x, cfg, training, stats):
 
 def subsample(W, cfg, src_tokens, src_lengths, training=False, trace=None):
     """conv_transformer.py:202-232: 2x[conv3x3 s2 p1 -> act -> BN] -> (cfg attn_2d: 2x residual ConvAttention2D,
-    :216-222) -> flatten (channel-major) -> fc3 -> act -> + positions.  Dropout is identity (parity mode).
+    :216-222) -> flatten (channel-major) -> fc3 -> act -> + positions.  Dropout: site_drop (identity without masks).
     Returns x (T4,B,D), lengths (B,), dict of updated BN running stats."""
     act = act_fn(cfg["act"])
     x = src_tokens.unsqueeze(1)
@@ -155,6 +189,7 @@ def subsample(W, cfg, src_tokens, src_lengths, training=False, trace=None):
                                  W[q + "running_var"], training, cfg["bn_momentum"], cfg["bn_eps"])
         stats[q + "running_mean"], stats[q + "running_var"] = rm, rv
         lengths = torch.ceil(lengths.float() / 2).long()          # :213
+        x = site_drop(cfg, "encoder.conv%d.drop" % i, x)          # :214 (rate max(dropout, 0.1)); layouts (B,C,T2,F2), (B,C,T4,F4)
         if trace is not None:
             trace["conv%d" % i] = x
     if cfg.get("attn_2d"):
@@ -172,17 +207,19 @@ def subsample(W, cfg, src_tokens, src_lengths, training=False, trace=None):
     x = x + table[pos].transpose(0, 1)                                         # :229
     if cfg.get("layernorm_embedding"):                                         # :230-231 (before the dropout of :232)
         x = layer_norm(W, "encoder.layernorm_embedding.", x, cfg["ln_eps"])
+    x = site_drop(cfg, "encoder.embed.drop", x)                                # :232, (T4,B,D)
     if trace is not None:
         trace["embed"] = x
     return x, lengths, stats
 
 
 # ------------------------------------------------------------------ attention (a7, a13)
-def mha(W, pfx, heads, query, key, key_padding_mask=None, causal=False, dist_penalty=False, probs_out=None):
+def mha(W, pfx, heads, query, key, key_padding_mask=None, causal=False, dist_penalty=False, probs_out=None, drop=None):
     """fairseq/modules/multihead_attention.py:108-366 / F.multi_head_attention_forward
     (Appendix B1): q,k,v projections with bias, q * d^-1/2, -inf on padded keys and
     above the diagonal (causal), softmax in fp32, P.V, out-projection.
-    query (Tq,B,D), key (Tk,B,D) -> (Tq,B,D)."""
+    query (Tq,B,D), key (Tk,B,D) -> (Tq,B,D).  drop = (keep [B,H,Tq,Tk], p): site_drop's arithmetic on the probabilities
+    (site `pfx + "probs"`; multihead_attention.py:342-346)."""
     Tq, B, D = query.shape
     Tk = key.shape[0]
     d = D // heads
@@ -208,6 +245,8 @@ def mha(W, pfx, heads, query, key, key_padding_mask=None, causal=False, dist_pen
         # need_weights / need_head_weights (multihead_attention.py:342-355): the softmax output (before dropout) as
         # (heads, B, Tq, Tk); the decoder averages the first `alignment_heads` of them (transformer.py:772-777)
         probs_out.append(p.view(B, heads, Tq, Tk).transpose(0, 1))
+    if drop is not None:
+        p = site_drop({"drop_masks": {"probs": drop}}, "probs", p)
     o = torch.bmm(p, v).transpose(0, 1).contiguous().view(Tq, B, D)
     return F.linear(o, W[pfx + "out_proj.weight"], W[pfx + "out_proj.bias"])
 
@@ -216,25 +255,31 @@ def layer_norm(W, pfx, x, eps=1e-5):
     return F.layer_norm(x, (x.shape[-1],), W[pfx + "weight"], W[pfx + "bias"], eps)
 
 
-def ffn(W, pfx, x, act):
-    return F.linear(act(F.linear(x, W[pfx + "fc1.weight"], W[pfx + "fc1.bias"])),
-                    W[pfx + "fc2.weight"], W[pfx + "fc2.bias"])
+def ffn(W, pfx, x, act, cfg=None):
+    """fc2(dropout(act(fc1 x))), then the dropout on the block's output (transformer_layer.py:132-135, 358-361)"""
+    a = act(F.linear(x, W[pfx + "fc1.weight"], W[pfx + "fc1.bias"]))
+    if cfg is not None:
+        a = site_drop(cfg, pfx + "ffn.act", a)
+    y = F.linear(a, W[pfx + "fc2.weight"], W[pfx + "fc2.bias"])
+    return y if cfg is None else site_drop(cfg, pfx + "ffn.out", y)
 
 
 def encoder_layer(W, cfg, pfx, x, pad_mask):
-    """fairseq/modules/transformer_layer.py:87-139 (dropout = identity)."""
+    """fairseq/modules/transformer_layer.py:87-139 (dropout: site_drop at :123, :133, :135 and on the attention probabilities)."""
     act = act_fn(cfg["act"])
     pre = cfg["enc_pre_ln"]
     r = x
     if pre:
         x = layer_norm(W, pfx + "self_attn_layer_norm.", x)
-    x = r + mha(W, pfx + "self_attn.", cfg["heads"], x, x, pad_mask, dist_penalty=bool(cfg.get("distance_penalty", False)))
+    x = r + site_drop(cfg, pfx + "self_attn.out", mha(W, pfx + "self_attn.", cfg["heads"], x, x, pad_mask,
+                                                     dist_penalty=bool(cfg.get("distance_penalty", False)),
+                                                     **_probs_drop(cfg, pfx + "self_attn.probs")))
     if not pre:
         x = layer_norm(W, pfx + "self_attn_layer_norm.", x)
     r = x
     if pre:
         x = layer_norm(W, pfx + "final_layer_norm.", x)
-    x = r + ffn(W, pfx, x, site_act(cfg, pfx + "ffn", act))
+    x = r + ffn(W, pfx, x, site_act(cfg, pfx + "ffn", act), cfg)
     if not pre:
         x = layer_norm(W, pfx + "final_layer_norm.", x)
     return x
@@ -298,6 +343,7 @@ def decoder_forward(W, cfg, prev_output_tokens, enc_out, enc_pad_mask, pfx="deco
     x = x + table[token_positions(prev_output_tokens, pad)]                   # :728-729
     if cfg.get("layernorm_embedding"):                                         # :731-732
         x = layer_norm(W, pfx + "layernorm_embedding.", x, cfg["ln_eps"])
+    x = site_drop(cfg, pfx + "embed.drop", x)                                  # :734, (B,L,D)
     x = x.transpose(0, 1)
     self_pad = prev_output_tokens.eq(pad)
     self_pad = self_pad if bool(self_pad.any()) else None                     # :739-741
@@ -311,14 +357,16 @@ def decoder_forward(W, cfg, prev_output_tokens, enc_out, enc_pad_mask, pfx="deco
         r = x
         if pre:
             x = layer_norm(W, p + "self_attn_layer_norm.", x)
-        x = r + mha(W, p + "self_attn.", cfg["heads"], x, x, self_pad, causal=True)
+        x = r + site_drop(cfg, p + "self_attn.out", mha(W, p + "self_attn.", cfg["heads"], x, x, self_pad, causal=True,
+                                                       **_probs_drop(cfg, p + "self_attn.probs")))
         if not pre:
             x = layer_norm(W, p + "self_attn_layer_norm.", x)
         r = x
         if pre:
             x = layer_norm(W, p + "encoder_attn_layer_norm.", x)
         probs = [] if l == attn_layer else None
-        x = r + mha(W, p + "encoder_attn.", cfg["heads"], x, enc_out, enc_pad_mask, probs_out=probs)
+        x = r + site_drop(cfg, p + "encoder_attn.out", mha(W, p + "encoder_attn.", cfg["heads"], x, enc_out, enc_pad_mask,
+                                                          probs_out=probs, **_probs_drop(cfg, p + "encoder_attn.probs")))
         if probs:
             attn = probs[0][:attn_heads].mean(dim=0) if attn_heads is not None else probs[0].mean(dim=0)
         if not pre:
@@ -326,7 +374,7 @@ def decoder_forward(W, cfg, prev_output_tokens, enc_out, enc_pad_mask, pfx="deco
         r = x
         if pre:
             x = layer_norm(W, p + "final_layer_norm.", x)
-        x = r + ffn(W, p, x, site_act(cfg, p + "ffn", act))
+        x = r + ffn(W, p, x, site_act(cfg, p + "ffn", act), cfg)
         if not pre:
             x = layer_norm(W, p + "final_layer_norm.", x)
     if pre:

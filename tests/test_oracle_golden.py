@@ -99,6 +99,63 @@ def test_ctc_multi_loss_and_grads(name):
             close(Wg[k[5:]].grad, g[k], tol=2e-4, what=k)
 
 
+@pytest.mark.parametrize("case", ["relu", "lne"])
+def test_dropout_sites_sit_where_the_reference_puts_them(case):
+    """One train-mode ctc_multi_loss update of the real reference WITH dropout (0.2 / attention 0.1 / activation 0.15, subsampler
+    max(0.2, 0.1)), its F.dropout replaced by a recorder that draws every call's keep mask itself (tests/golden/make_dropout_fixture.py,
+    fixture dropout.npz).  The oracle, given those masks mapped from call order to its site names (s2t_ref.drop_sites), reproduces the
+    loss to 1e-4 and every gradient norm and stored gradient to 5e-4: a site the oracle forgot, scaled twice, or placed on the other
+    side of a residual or a LayerNorm (case `lne`: both embedding masks sit behind their LayerNorm) fails here."""
+    g = {k[len(case) + 1:]: v for k, v in load_golden("dropout").items() if k.startswith(case + "_")}
+    D, H, Ff, EL, DL, ctc_layer, compress, V_src, V_tgt, blank, seed = [int(v) for v in g["meta"]]
+    cfg = s2t_ref.default_cfg(D=D, heads=H, ffn=Ff, enc_layers=EL, dec_layers=DL, ctc_layer=ctc_layer, layernorm_embedding=(case == "lne"))
+    W = s2t_ref.make_weights(s2t_ref.param_shapes(cfg, V_src, V_tgt, criterion_fc=True), seed)
+    t = lambda k: torch.from_numpy(g["in_" + k])
+    sample = dict(ntokens=int(g["in_ntokens"]), net_input=dict(src_tokens=t("src_tokens"), src_lengths=t("src_lengths"),
+                  prev_output_tokens=t("prev_output_tokens")), target=t("target"), transcript_target=t("transcript_target"),
+                  transcript_target_lengths=t("transcript_target_lengths"), ctc_encoder_layer=ctc_layer)
+    sites = s2t_ref.drop_sites(cfg)
+    assert int(g["n_calls"]) == len(sites) == 3 + 4 * EL + 1 + 6 * DL, "the reference called F.dropout %d times, the oracle has %d sites" % (
+        int(g["n_calls"]), len(sites))
+    p_drop, p_attn, p_act = [float(v) for v in g["rates"]]
+    bits = np.unpackbits(g["mask_bits"]).astype(bool)
+    masks, off = {}, 0
+    for site, shp, p in zip(sites, g["mask_shapes"], g["mask_p"]):
+        shp = tuple(int(v) for v in shp if v > 0)
+        n = int(np.prod(shp))
+        masks[site] = (torch.from_numpy(bits[off:off + n].reshape(shp).copy()), float(p))
+        off += n
+        want = p_attn if site.endswith(".probs") else p_act if site.endswith("ffn.act") else max(p_drop, 0.1) if ".conv" in site else p_drop
+        assert float(p) == want, (site, float(p), want)                 # the rate of every site, the subsampler's max(p, 0.1) included
+    assert off + 8 > bits.size >= off
+    B, T4, L = sample["net_input"]["src_tokens"].shape[0], masks["encoder.embed.drop"][0].shape[0], sample["target"].shape[1]
+    assert masks["encoder.embed.drop"][0].shape == (T4, B, D) and masks["decoder.embed.drop"][0].shape == (B, L, D)
+    assert masks["encoder.layers.0.self_attn.probs"][0].numel() == B * H * T4 * T4
+    cfg_m = dict(cfg, drop_masks=masks)
+    Wg = {k: v.clone().requires_grad_(v.dtype.is_floating_point and "running" not in k) for k, v in W.items()}
+    loss, ss, log, enc, logits, _ = s2t_ref.ctc_multi_loss(Wg, cfg_m, sample, 0.1, 1.0, blank, training=True)
+    loss.backward()
+    assert int(enc.new_lengths.min()) < T4, "the case must compress"
+    ref = float(g["train_loss"])
+    assert abs(float(loss) - ref) <= 1e-4 * max(1.0, abs(ref)), (float(loss), ref)
+    assert ss == int(g["train_sample_size"])
+    for k in ("ctc_loss", "nll_loss", "ntokens", "nsentences", "sample_size", "ctc_errors", "ctc_total", "nframes"):
+        close(log[k], float(g["train_log_" + k]), what=k)
+    for k, r in zip([str(k) for k in g["gradnorm_keys"]], g["gradnorm_vals"]):
+        mine = float(Wg[k].grad.norm()) if (k in Wg and Wg[k].grad is not None) else 0.0
+        assert abs(mine - r) <= 5e-4 * max(1.0, r), (k, mine, r)
+    n_full = 0
+    for k in g:
+        if k.startswith("grad_"):
+            close(Wg[k[5:]].grad, g[k], tol=5e-4, what=k)
+            n_full += 1
+    assert n_full >= 20
+    # the masks matter: without them the same oracle is far from the reference's loss
+    with torch.no_grad():
+        plain = s2t_ref.ctc_multi_loss(W, cfg, sample, 0.1, 1.0, blank, training=True)[0]
+    assert abs(float(plain) - ref) > 1e-3 * abs(ref)
+
+
 def test_optimizer_steps():
     g, cfg, W, sample, meta = model_case("model_a")
     P = {k: v.clone() for k, v in W.items()}
