@@ -606,6 +606,39 @@ def ensemble_lse(lprobs):
     return out
 
 
+def score_targets(logits_list, target):
+    """log-probability of target[b][t] under each position's distribution, for one model or the log of the mean probability of up to
+    eight (include/s2t_hip.h s2t_score_targets).  logits_list: (B, L, V) views of time-major buffers of one dtype, what
+    `model(**net_input)[0]` is: their storage is taken as it is when rows t*B + b are evenly strided (any row stride >= V), else copied
+    once into time-major order.  target: int64 [B, L].  Returns f32 [B, L]; a target outside [0, V) gives NaN."""
+    n = len(logits_list)
+    if not 1 <= n <= 8:
+        raise ValueError("score_targets takes 1..8 members (s2t_score_targets), got %d" % n)
+    B, Ln, V = logits_list[0].shape
+    if tuple(target.shape) != (B, Ln) or target.dtype != torch.int64:
+        raise ValueError("score_targets: target must be int64 [%d, %d], got %s %s" % (B, Ln, target.dtype, tuple(target.shape)))
+    keep, ptrs, lds = [], [], []
+    for x in logits_list:
+        if tuple(x.shape) != (B, Ln, V) or x.dtype != logits_list[0].dtype:
+            raise ValueError("score_targets: members differ in shape or dtype (%s %s against %s %s)"
+                             % (x.dtype, tuple(x.shape), logits_list[0].dtype, (B, Ln, V)))
+        lt = x.transpose(0, 1)
+        # the check of criterions._KDFn.forward; the stride torch reports for a size-1 dimension is arbitrary (see _row_ld)
+        ld = lt.stride(1) if B > 1 else (lt.stride(0) if Ln > 1 else V)
+        if lt.stride(2) != 1 or ld < V or (B > 1 and Ln > 1 and lt.stride(0) != B * ld):
+            lt, ld = lt.contiguous(), V
+        keep.append(lt)
+        ptrs.append(L.ptr(lt))
+        lds.append(ld)
+    target = target.contiguous()
+    out = torch.empty((B, Ln), dtype=torch.float32, device=target.device)
+    parr = (ctypes.c_void_p * n)(*ptrs)
+    larr = (ctypes.c_int * n)(*lds)
+    L.check(_lib().s2t_score_targets(L.dt(logits_list[0]), n, ctypes.addressof(parr), ctypes.addressof(larr), L.ptr(target), L.ptr(out),
+                                     B, Ln, V, L.stream()), "s2t_score_targets")
+    return out
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

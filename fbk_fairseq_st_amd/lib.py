@@ -65,6 +65,7 @@ SIGNATURES = {
     "s2t_softmax_probs": [c_int, P, P, c_long, c_int, c_int, c_float, P],
     "s2t_softmax_bwd": [c_int, P, P, P, c_long, c_int, c_int, c_float, c_int, P],
     "s2t_ensemble_lse": [c_int, P, P, c_size_t, P],
+    "s2t_score_targets": [c_int, c_int, P, P, P, P, c_int, c_int, c_int, P],
     "s2t_embed_bwd": [c_int, P, P, P, c_int, c_int, c_int, c_float, c_int, P],
     "s2t_act_bwd": [c_int, P, P, P, c_size_t, c_int, c_float, c_ull, P],
     "s2t_add_inplace": [c_int, P, P, c_size_t, P],

@@ -357,9 +357,11 @@ class FairseqTask(_TaskBase):
         if sampling:
             raise NotImplementedError("--sampling is not opened through build_generator yet: hand SequenceGenerator a "
                                       "search_strategy=sequence_generator.Sampling(tgt_dict, sampling_topk, sampling_topp, seed=...)")
-        for flag in ("score_reference", "match_source_len"):
-            if getattr(args, flag, False):
-                raise NotImplementedError("--%s is outside the S2T hot path" % flag.replace("_", "-"))
+        if getattr(args, "score_reference", False):
+            raise NotImplementedError("--score-reference is not opened through build_generator yet: hand task.inference_step a "
+                                      "sequence_scorer.SequenceScorer(tgt_dict, compute_alignment=...) in place of the generator")
+        if getattr(args, "match_source_len", False):
+            raise NotImplementedError("--match-source-len is outside the S2T hot path")
         if rate > 0:
             # fairseq/search.py:338 takes the beam of a candidate with torch.div on integers, which is true division in current torch: the
             # reference's own DiverseSiblingsSearch hands float beam indices to the generator, so there is no behaviour to reproduce

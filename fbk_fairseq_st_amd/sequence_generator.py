@@ -169,6 +169,20 @@ class Sampling:
         return lp + (prev_scores[:, :, 0] if step == 0 else scores[:, :, step - 1]), tok, torch.arange(beam, device=dev).repeat(B, 1)
 
 
+def hard_alignment(attn, tgt_tokens, pad, eos):
+    """SequenceGeneratorWithAlignment.generate for a model without full-context alignment (sequence_generator.py:830-841) +
+    fairseq/utils.py:486-503 extract_hard_alignment: for every target position that is neither pad nor EOS, the source position
+    with the largest attention weight, as (source, target) pairs.  attn: Ts x target length.  The source side of this model is
+    filterbank frames, so the reference's token-to-word mapping has nothing to map: the pair holds the 0-based index on the axis the
+    attention is over (the encoder's output frames, after subsampling and CTC compression) and the 0-based target position.  Index
+    work only.  Shared by SequenceGenerator (--print-alignment) and sequence_scorer.SequenceScorer (compute_alignment)."""
+    valid = (tgt_tokens.ne(pad) & tgt_tokens.ne(eos)).nonzero(as_tuple=False).view(-1)
+    if attn.numel() == 0 or valid.numel() == 0:
+        return []
+    _, src_idx = attn.t()[valid.to(attn.device)].max(dim=1)
+    return list(zip(src_idx.tolist(), valid.tolist()))
+
+
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True, len_penalty=1.0,
                  unk_penalty=0.0, retain_dropout=False, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
@@ -236,16 +250,7 @@ class SequenceGenerator:
         return hyps
 
     def _hard_alignment(self, attn, src_len, tgt_tokens):
-        """SequenceGeneratorWithAlignment.generate for a model without full-context alignment (sequence_generator.py:830-841) +
-        fairseq/utils.py:486-503 extract_hard_alignment: for every target position that is neither pad nor EOS, the source position
-        with the largest attention weight, as (source, target) pairs.  The source side of this model is filterbank frames, so the
-        reference's token-to-word mapping has nothing to map: the pair holds the 0-based index on the axis the attention is over (the
-        encoder's output frames, after subsampling and CTC compression) and the 0-based target position.  Index work only."""
-        valid = (tgt_tokens.ne(self.pad) & tgt_tokens.ne(self.eos)).nonzero(as_tuple=False).view(-1)
-        if attn.numel() == 0 or valid.numel() == 0:
-            return []
-        _, src_idx = attn.t()[valid.to(attn.device)].max(dim=1)
-        return list(zip(src_idx.tolist(), valid.tolist()))
+        return hard_alignment(attn, tgt_tokens, self.pad, self.eos)
 
     def _expand(self, decoder, enc, B):
         """encoder output with one copy per hypothesis slot (sequence_generator.py:176-196)"""

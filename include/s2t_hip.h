@@ -337,6 +337,22 @@ int s2t_softmax_bwd(int dtype, const float* out, const float* dout, void* dlogit
 /* ensemble of n <= 8 models (fairseq/sequence_generator.py:757-768 EnsembleModel.forward_decoder): out = logsumexp_j lprobs[j] - log n,
  * element-wise over numel f32 values; `lprobs` is a HOST array of n device pointers */
 int s2t_ensemble_lse(int n, const float* const* lprobs, float* out, size_t numel, void* stream);
+/* log-probability of the target token at every position of a teacher-forced forward (fairseq/sequence_scorer.py:42-92), for one
+ * model or the log of the mean probability of n <= 8 (`logits` and `ld` are HOST arrays of n device pointers / row strides, as
+ * s2t_ensemble_lse takes its members).  logits[j]: rows in the engine's time-major order, row r = t*B + b, V columns of `dtype`, row
+ * stride ld[j] >= V elements; target (int64) and out (f32): batch-major [B][L].  All arithmetic in f32, per member j and row r with
+ * x = logits[j][r][0..V) and c = target[b][t]:
+ *     m_j = max_v x_v;  s_j = sum_v exp(x_v - m_j);  lp_j = x_c - (m_j + log s_j)
+ *     n == 1: out[b][t] = lp_0;   n > 1: M = max_j lp_j; -inf if M is, else M + log(sum_j exp(lp_j - M)) - log n (members in order:
+ *     the combine of s2t_ensemble_lse);   c < 0 or c >= V: NaN, and nothing outside the row is read.
+ * No column is special (the pad index is a column like any other); columns [V, ld) never reach a result.  Every logit is read once
+ * (running max / sum), in 16-byte loads when every member's base and row stride are multiples of 16 bytes; no [rows, V]
+ * intermediate exists and V is limited by int only.  Deterministic: no atomics, a reduction tree fixed by column, identical in both
+ * launch forms (a workgroup per row below 4,096 rows, a wave per row from there), so a row's result does not depend on B, L or the grid.
+ * S2T_OK at once for B*L == 0; S2T_EINVAL for n < 1, n > 8, a NULL array / member / target / out, V < 1, any ld[j] < V, negative B or
+ * L, B*L > 2^31 - 1; S2T_ENOTSUP for a dtype other than bf16 / f32 -- all before anything is launched. */
+int s2t_score_targets(int dtype, int n, const void* const* logits, const int* ld, const long long* target, float* out,
+                      int B, int L, int V, void* stream);
 int s2t_embed_bwd(int dtype, const long long* tokens, const void* dout, float* dW, int B, int L, int D,
                   float scale, int pad, void* stream);
 /* out = dropout(dy) * act'(y): act 1 = relu (y = post-activation), act 2 = gelu (y = pre-activation); the dropout (p_drop > 0, mask
