@@ -115,7 +115,20 @@ struct AttnArgs {
     int B, H, Tq, Tk, causal;
     int dist_pen;                                          // 1: scores -= max(0, ln|query - key|)  (LocalAttention + LogPenalty)
     float scale, p_drop; unsigned long long seed;
+    uint32_t* keep;                                        // dropout keep-bit record (s2t_attn_fwd_keep / s2t_attn_bwd_keep), null = hash
 };
+
+// ---- the dropout keep-bit record (include/s2t_hip.h, s2t_attn_keep_bytes) -------------------------------------------------------
+// One bit per (query, key) pair in the register layout attn_fwd2_kernel and attn_bwd_dq2_kernel share (query = lane, four keys per
+// accumulator): one 32-bit word per lane and 64-key tile,
+//     word  (((b H + h) ceil(Tq / 128) + bx) ceil(Tk / 64) + t) 256 + threadIdx.x
+//     bit   16 qb + 4 j + r  of lane (r16, q) of wave w  =  keep(query 128 bx + 32 w + 16 qb + r16, key 64 t + 16 j + 4 q + r).
+// The forward writes the decisions its hash produced; the backward kernels test the bits where they would hash again.  Key tiles at
+// or past klen[b] are not written and bits of queries >= Tq or keys >= klen[b] mean nothing: those probabilities are exact zeros or
+// never stored.
+__device__ __forceinline__ size_t keep_block(const AttnArgs& p, int head, int bx, int t) {
+    return (((size_t)head * ((p.Tq + 127) >> 7) + bx) * ((p.Tk + 63) >> 6) + t) * 256;
+}
 
 // dropout element index of (b, h, query, key): key rows are padded to a multiple of 4 so that 4 consecutive keys from a
 // multiple of 4 form one hash quad (common.hpp drop_hash4) in every kernel's register layout
@@ -132,6 +145,14 @@ __device__ __forceinline__ float drop_scale(const AttnArgs& p, int b, int h, int
 // saturating field - (th - 1) is not zero.  thm1x2 = (th - 1) in both halves.
 __device__ __forceinline__ uint32_t drop_pair(uint32_t pair, uint32_t fields, uint32_t thm1x2) {
     uint32_t d, k, r;
+    asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(fields), "v"(thm1x2));
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(k) : "v"(d), "v"(0x00010001u));
+    asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(pair), "v"(k));
+    return r;
+}
+// the same, handing out the 0 / 1 keep decisions (bits 0 and 16) it multiplied by
+__device__ __forceinline__ uint32_t drop_pair_k(uint32_t pair, uint32_t fields, uint32_t thm1x2, uint32_t& k) {
+    uint32_t d, r;
     asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(fields), "v"(thm1x2));
     asm("v_pk_min_u16 %0, %1, %2" : "=v"(k) : "v"(d), "v"(0x00010001u));
     asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(pair), "v"(k));
@@ -319,6 +340,8 @@ extern "C" int s2t_dbg_attn_stamps(void* buf) {
 #define ASTAMP(T, K)
 #define ASTAMP_EARLY(KID)
 #endif
+// KEEP: also write the dropout keep-bit record (plain softmax with dropout on only: every tile is a FAST && DROP tile)
+template <bool KEEP>
 __global__ __launch_bounds__(256, 3) void attn_fwd2_kernel(AttnArgs p) {
     constexpr int DH = 64;
     ASTAMP_EARLY(0)
@@ -441,6 +464,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd2_kernel(AttnArgs p) {
         // row sum, a share of the bf16 pair convert, and for dropout a 16-bit compare + select on the value.  The 1/(1-p) of the
         // dropout is a constant factor of O: it is applied once, with the 1/l normalisation, at the end.
         u32x4 pf[2][2];                                // [query block][32-key block]
+        uint32_t keepw = 0u;                           // KEEP: this lane's word of the record for tile t
         // Two instantiations: FAST = interior tile of a plain softmax with an index space below 2^34 elements (no masks, no
         // distance penalty, the dropout quad index stays in its low word); the other handles everything dynamically.
         auto softmax_tile = [&](auto fast_tag, auto drop_tag) {
@@ -476,6 +500,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd2_kernel(AttnArgs p) {
                 const bool drop = FAST ? DROP : has_drop;
                 const uint64_t quad0 = drop ? drop_index(p, b, h, qrow, kv0 + 4 * q) >> 2 : 0;
                 const uint32_t qlo = (uint32_t)quad0, hwm0 = drop_high_mix(p.seed, quad0);
+                uint32_t k01s = 0u, k23s = 0u;         // KEEP: decisions of keys r = 0 / 1 (bits 4 j, 16 + 4 j) and r = 2 / 3
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float pv[4];
@@ -484,7 +509,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd2_kernel(AttnArgs p) {
                     rs2 += (f32x2_t){pv[0], pv[1]};
                     rs2 += (f32x2_t){pv[2], pv[3]};
                     uint32_t p01 = pack_bf16(pv[0], pv[1]), p23 = pack_bf16(pv[2], pv[3]);
-                    if (drop) {
+                    if constexpr (KEEP && FAST && DROP) {
+                        // the 0 / 1 fields the packed product multiplies by ARE the record's bits: no second hash, one shift-or each
+                        const u32x2 hq = drop_hash4_lo(drop_ks, hwm0, qlo + 4u * j);
+                        uint32_t k01, k23;
+                        p01 = drop_pair_k(p01, hq[1], drop_thm1x2, k01); p23 = drop_pair_k(p23, hq[0], drop_thm1x2, k23);
+                        k01s |= k01 << (4 * j); k23s |= k23 << (4 * j);
+                    } else if (drop) {
                         // the mask on the PACKED pairs: the hash words hold the 16-bit fields in the order of the pairs (fields 0, 1 =
                         // y.lo, y.hi; 2, 3 = x.lo, x.hi), so "field >= threshold" is a saturating packed subtract of threshold - 1,
                         // a packed min with 1, and the packed product of the bf16 bit patterns with that 0 / 1: 3 VALU per pair
@@ -495,14 +526,25 @@ __global__ __launch_bounds__(256, 3) void attn_fwd2_kernel(AttnArgs p) {
                     pf[qb][j >> 1][2 * (j & 1)] = p01;
                     pf[qb][j >> 1][2 * (j & 1) + 1] = p23;
                 }
+                if constexpr (KEEP && FAST && DROP) {
+                    // bits 4 j + {0, 2} and 16 + 4 j + {0, 2}: fold the upper half down by 15 -> bit 4 j + r of this query block's half
+                    const uint32_t tw = k01s | (k23s << 2), hw = tw | (tw >> 15);
+                    keepw |= qb == 0 ? (hw & 0xffffu) : (hw << 16);
+                }
                 l[qb] = l[qb] * alpha + (rs2[0] + rs2[1]);
 #pragma unroll
                 for (int n = 0; n < 4; ++n) o[qb][n] *= alpha;
             }
         };
-        if (!plain) softmax_tile(std::false_type{}, std::false_type{});
-        else if (has_drop) softmax_tile(std::true_type{}, std::true_type{});
-        else softmax_tile(std::true_type{}, std::false_type{});
+        if constexpr (KEEP) {                          // launched only for a plain softmax with a rate of 2^-16 or more
+            softmax_tile(std::true_type{}, std::true_type{});
+            // a wave stores 256 contiguous bytes; uniform base + 32-bit lane offset
+            *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(p.keep + keep_block(p, head, bx, t)) + threadIdx.x * 4u) = keepw;
+        } else {
+            if (!plain) softmax_tile(std::false_type{}, std::false_type{});
+            else if (has_drop) softmax_tile(std::true_type{}, std::true_type{});
+            else softmax_tile(std::true_type{}, std::false_type{});
+        }
         ASTAMP(t, 2)
         // ---- O^T += V^T P^T
 #pragma unroll
@@ -817,10 +859,12 @@ __device__ __forceinline__ void stage2_dma(const bf16* A, long a_st, const bf16*
 }
 #define S2T_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)               /* vmcnt(0); lgkmcnt / expcnt untouched */
 
+// KEEP: the keep decisions come from the forward's record (plain softmax, dropout on), not from the hash
+template <bool KEEP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
     constexpr int DH = 64;
     ASTAMP_EARLY(2)
-    extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 stages x (Q 8 KiB | dO 8 KiB)
+    extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 stages x (Q 8 KiB | dO 8 KiB), statistics, own K / V, KEEP: 2 x 1 KiB of record
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r16 = lane & 15, q = lane >> 4;
     int head;
     const int bx = head_xcd_remap(head, p.B * p.H, gridDim.x);
@@ -853,8 +897,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
     const int ntile = qstart < p.Tq ? (p.Tq - qstart + 63) / 64 : 0;
     // per-query statistics of the tile (LSE, Delta) travel with it: 4-byte LDS-DMA by waves 0 / 1
     float* sStat = reinterpret_cast<float*>(smem + 32768);          // [2 stages][2][64]
+    // KEEP: the record words of a 64-query tile and the workgroup's 128 keys travel with the tile: 2 forward waves x 2 key tiles x 64
+    // lanes = 1 KiB, [key tile][forward wave & 1][lane], one 4-byte LDS-DMA per thread (a wave moves 256 contiguous bytes).  The
+    // second key tile of the last workgroup may not exist: it is clamped, its keys (>= Tk) are never stored.
+    char* sKeep = smem + 32768 + 1024 + 32768;                      // [2 stages][2][128] words
+    const int nkt = (p.Tk + 63) >> 6;
+    const uint32_t keep_sh = 8 * (wave & 1) + (r16 & 3);            // the own key's part of its record bit
     auto stage = [&](int qt, int stg) {
         stage2_dma(Qg, p.q_st, dOg, p.do_st, qt, p.Tq, smem + stg * 16384, wave, lane);
+        if constexpr (KEEP) {
+            const uint32_t* blk = p.keep + keep_block(p, head, qt >> 7, min(2 * bx + (wave >> 1), nkt - 1)) + ((qt >> 6) & 1) * 128;
+            const char* src = reinterpret_cast<const char*>(blk) + (uint32_t)(((wave & 1) * 64 + lane) * 4);
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)src,
+                                             (__attribute__((address_space(3))) void*)(sKeep + stg * 1024 + wave * 256), 4, 0, 0);
+        }
         if (wave < 2) {
             // rows past Tq (the last tile): LSE = +inf, so their probabilities -- and with them dS -- are exact zeros without a mask
             // per element (their Q / dO rows repeat the last query: finite); the DMA writes nothing for the lanes that are off
@@ -899,6 +955,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
         const char* sQ = smem + (t & 1) * 16384;
         const char* sDO = sQ + 8192;
         const float* sL = sStat + (t & 1) * 128;
+        const char* sKp = sKeep + (t & 1) * 1024 + (wave >> 1) * 512 + ((r16 >> 2) * 16 + 4 * q) * 4;
         ASTAMP(t, 0)
         if (t + 1 < ntile) stage(qt + 64, (t + 1) & 1);
         ASTAMP(t, 1)
@@ -919,7 +976,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
             const f32x4 L = *reinterpret_cast<const f32x4*>(sL + 16 * i + 4 * q) * 1.44269504088896f;
             const f32x4 Dl = *reinterpret_cast<const f32x4*>(sL + 64 + 16 * i + 4 * q);
             // dropout: lane r16 hashes (query 4q + (r16 & 3), key quad r16 >> 2) of both key blocks
-            const uint32_t qrow_quads = DROP ? (uint32_t)(((b * p.H + h) * p.Tq + qt + 16 * i + 4 * q + (r16 & 3))) * tkq : 0u;
+            const uint32_t qrow_quads = (DROP && !KEEP) ? (uint32_t)(((b * p.H + h) * p.Tq + qt + 16 * i + 4 * q + (r16 & 3))) * tkq : 0u;
+            // KEEP: queries 16 i + 4 q + r, r = 0..3, are lanes 4 q + r of row r16 >> 2 of forward wave i / 2: four consecutive words.
+            // The own key 32 (wave & 1) + 16 kb + r16 of its 64-key tile is bit 16 (i & 1) + 4 (2 (wave & 1) + kb) + (r16 & 3): the
+            // lane-dependent part is shifted out once per four queries and both key blocks, the rest is a constant per element.
+            u32x4 kws = {0u, 0u, 0u, 0u};
+            if constexpr (KEEP) {
+                kws = *reinterpret_cast<const u32x4*>(sKp + (i >> 1) * 256);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) kws[r] >>= keep_sh;
+            }
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
                 f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
@@ -936,7 +1002,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
                 // key) then costs one DPP quad broadcast fused into an AND with the own key's bit, one compare and the two selects --
                 // broadcasting both hash words and extracting a lane-dependent 16-bit field per element took 2.4x as many instructions.
                 uint32_t nib = 0u;
-                if constexpr (DROP) {
+                if constexpr (DROP && !KEEP) {
                     const u32x2 hq = drop_hash4_lo(drop_ks, drop_hwm, qrow_quads + ((uint32_t)key >> 2));
                     uint32_t dy, dx, ky, kx;
                     asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dy) : "v"(hq[1]), "v"(drop_thm1x2));
@@ -955,7 +1021,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
                     if constexpr (EDGE) e = (qrow < p.Tq && (!p.causal || key <= qrow)) ? e : 0.f;     // keys past klen: discarded at the store
                     if constexpr (DROP) {
                         // the bits of (query 4q + r, keys of the own quad) sit in lane (r16 & ~3) | r of the same 4-lane group
-                        const bool keep = (quad_bcast(nib, r) & own_bit) != 0u;
+                        bool keep;
+                        if constexpr (KEEP) keep = (kws[r] & (1u << (16 * (i & 1) + 4 * kb))) != 0u;
+                        else keep = (quad_bcast(nib, r) & own_bit) != 0u;
                         pv[r] = keep ? e : 0.f;
                         ds[r] = e * __builtin_fmaf(keep ? dp[r] : 0.f, drop_inv, -Dl[r]);
                     } else {
@@ -979,7 +1047,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
         }
         };
         const bool edge = generic;                       // a plain softmax has no edge: the query tail is handled by LSE = +inf
-        if (p.p_drop > 0.f) { if (edge) tile(std::true_type{}, std::true_type{}); else tile(std::false_type{}, std::true_type{}); }
+        if constexpr (KEEP) tile(std::false_type{}, std::true_type{});
+        else if (p.p_drop > 0.f) { if (edge) tile(std::true_type{}, std::true_type{}); else tile(std::false_type{}, std::true_type{}); }
         else if (edge) tile(std::true_type{}, std::false_type{});
         else tile(std::false_type{}, std::false_type{});
         ASTAMP(t, 3)
@@ -1011,6 +1080,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {
     ASTAMP(7, 3)
 }
 
+// KEEP: the keep decisions come from the forward's record (same lane map: the lane's own word per key tile), not from the hash
+template <bool KEEP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
     constexpr int DH = 64;
     ASTAMP_EARLY(1)
@@ -1080,6 +1151,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
 
     const float sc2 = p.scale * 1.44269504088896f;
     const bool generic = p.causal || p.dist_pen;
+    // KEEP: the record word of tile t + 1 is fetched behind tile t + 1's DMA and lands under the same wait
+    const char* keep_w = nullptr;
+    uint32_t kw_next = 0u;
+    if constexpr (KEEP) {
+        keep_w = reinterpret_cast<const char*>(p.keep + keep_block(p, head, bx, 0));       // uniform base, 32-bit lane offsets
+        if (ntile > 0) kw_next = *reinterpret_cast<const uint32_t*>(keep_w + threadIdx.x * 4u);
+    }
     // Q / dO fragments must have landed before the loop: left pending, the compiler's wait for them sits behind the loop's own
     // prefetch in the in-order counter and becomes a vmcnt(0), i.e. the whole K/V prefetch latency, exposed, every iteration
     S2T_WAIT_VM0();                                   // (the first K/V tile went out ahead of those loads: one round trip, not two)
@@ -1091,6 +1169,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
         const char* sV = sK + 8192;
         ASTAMP(t, 0)
         if (t + 1 < ntile) stage2_dma(Kg, p.k_st, Vg, p.v_st, kv0 + 64, p.Tk, smem + ((t + 1) & 1) * 16384, wave, lane);
+        const uint32_t kw = kw_next;
+        if constexpr (KEEP) { if (t + 1 < ntile) kw_next = *reinterpret_cast<const uint32_t*>(keep_w + ((uint32_t)(t + 1) * 1024u + threadIdx.x * 4u)); }
         ASTAMP(t, 1)
         u32x4 sf[2][2];                                 // [query block][32-key block]: dS^T as B operand
         // EDGE: masks per element (keys past klen -- their tile rows hold whatever lies there --, the causal triangle, the distance
@@ -1113,7 +1193,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
                 const int qrow = qw + 16 * qb + r16;
                 const int key0 = kv0 + 16 * j + 4 * q;
                 u32x2 hq = {0u, 0u};
-                if constexpr (DROP) hq = drop_hash4_lo(drop_ks, drop_hwm, (uint32_t)((b * p.H + h) * p.Tq + qrow) * tkq + ((uint32_t)key0 >> 2));   // keys 4q .. 4q+3 = one quad
+                if constexpr (DROP && !KEEP) hq = drop_hash4_lo(drop_ks, drop_hwm, (uint32_t)((b * p.H + h) * p.Tq + qrow) * tkq + ((uint32_t)key0 >> 2));   // keys 4q .. 4q+3 = one quad
                 float ds[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1126,7 +1206,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
                         e = (key < klen && (!p.causal || key <= qrow)) ? e : 0.f;
                     }
                     if constexpr (TAIL) e = (16 * j + r < tail_thr) ? e : 0.f;
-                    if constexpr (DROP) ds[r] = e * __builtin_fmaf(drop_field(hq, r) >= drop_th16 ? dp[r] : 0.f, drop_inv, -Dl[qb]);
+                    if constexpr (DROP && KEEP) ds[r] = e * __builtin_fmaf((kw & (1u << (16 * qb + 4 * j + r))) != 0u ? dp[r] : 0.f, drop_inv, -Dl[qb]);
+                    else if constexpr (DROP) ds[r] = e * __builtin_fmaf(drop_field(hq, r) >= drop_th16 ? dp[r] : 0.f, drop_inv, -Dl[qb]);
                     else ds[r] = e * (dp[r] - Dl[qb]);
                 }
                 sf[qb][j >> 1][2 * (j & 1)] = pack_bf16(ds[0], ds[1]); sf[qb][j >> 1][2 * (j & 1) + 1] = pack_bf16(ds[2], ds[3]);
@@ -1134,7 +1215,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs p) {
         }
         };
         const bool tail = kv0 + 64 > klen;
-        if (generic) { if (p.p_drop > 0.f) ds_tile(std::true_type{}, std::true_type{}, std::false_type{}); else ds_tile(std::true_type{}, std::false_type{}, std::false_type{}); }
+        if constexpr (KEEP) { if (tail) ds_tile(std::false_type{}, std::true_type{}, std::true_type{}); else ds_tile(std::false_type{}, std::true_type{}, std::false_type{}); }
+        else if (generic) { if (p.p_drop > 0.f) ds_tile(std::true_type{}, std::true_type{}, std::false_type{}); else ds_tile(std::true_type{}, std::false_type{}, std::false_type{}); }
         else if (p.p_drop > 0.f) { if (tail) ds_tile(std::false_type{}, std::true_type{}, std::true_type{}); else ds_tile(std::false_type{}, std::true_type{}, std::false_type{}); }
         else if (tail) ds_tile(std::false_type{}, std::false_type{}, std::true_type{});
         else ds_tile(std::false_type{}, std::false_type{}, std::false_type{});
@@ -1627,19 +1709,28 @@ template <typename T, int DH> static int bwd_launch(const AttnArgs& a, hipStream
         const bool idx32 = (unsigned long long)a.B * a.H * a.Tq * (unsigned long long)((a.Tk + 3) & ~3) < (1ull << 34);
         dkv2 = !v1 && al && idx32 && a.Tk >= 128 && span32(a.q_st, a.Tq) && span32(a.do_st, a.Tq);
         dq2 = !v1 && al && idx32 && span32(a.k_st, a.Tk) && span32(a.v_st, a.Tk) && (a.Tq >= 128 || (a.Tq >= S2T_ATTN_V2_MIN_TQ && a.Tk >= 128)) && !(a.o_st % 8) && !(a.o_sb % 8) && !((uintptr_t)a.O & 15);
+        // a.keep (checked by the caller: keep_route): each second-generation kernel that runs reads the record, a first-generation
+        // kernel next to it (dK/dV below 128 keys, a layout the second generation refuses) hashes -- the same decisions either way
         if (dq2) {                                       // first: it also writes Delta for the dK/dV kernel
-            hipLaunchKernelGGL(attn_bwd_dq2_kernel, dim3((a.Tq + 127) / 128, a.H, a.B), dim3(256), 32768, st, a);
+            if (a.keep) hipLaunchKernelGGL(attn_bwd_dq2_kernel<true>, dim3((a.Tq + 127) / 128, a.H, a.B), dim3(256), 32768, st, a);
+            else hipLaunchKernelGGL(attn_bwd_dq2_kernel<false>, dim3((a.Tq + 127) / 128, a.H, a.B), dim3(256), 32768, st, a);
             S2T_LAUNCH_CHECK();
         } else {
             hipLaunchKernelGGL((attn_delta_kernel<T, DH>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, st, a);
             S2T_LAUNCH_CHECK();
         }
         if (dkv2) {
+            constexpr int lds = 32768 + 1024 + 32768, lds_keep = lds + 2048;
             {
                 static bool attr = false;
-                if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 32768 + 1024 + 32768); attr = true; }
+                if (!attr) {
+                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv2_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv2_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_keep);
+                    attr = true;
+                }
             }
-            hipLaunchKernelGGL(attn_bwd_dkv2_kernel, dim3((a.Tk + 127) / 128, a.H, a.B), dim3(256), 32768 + 1024 + 32768, st, a);
+            if (a.keep) hipLaunchKernelGGL(attn_bwd_dkv2_kernel<true>, dim3((a.Tk + 127) / 128, a.H, a.B), dim3(256), lds_keep, st, a);
+            else hipLaunchKernelGGL(attn_bwd_dkv2_kernel<false>, dim3((a.Tk + 127) / 128, a.H, a.B), dim3(256), lds, st, a);
             S2T_LAUNCH_CHECK();
         }
     } else {
@@ -1677,12 +1768,32 @@ static int check_common(int dtype, int head_dim, const AttnArgs& a) {
     return S2T_OK;
 }
 
-extern "C" int s2t_attn_fwd(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+// ---- the keep-bit record: who gets one
+// The shapes whose forward is attn_fwd2_kernel on its FAST && DROP tiles -- exactly the ones the second-generation backward handles
+// on its plain path: bf16 (the caller's dtype), d = 64, no causal mask, no distance penalty, a dropout rate that drops something
+// (2^-16 or more), the 32-bit dropout quad index, and a query block the second generation takes that is not the short-query pair's.
+extern "C" size_t s2t_attn_keep_bytes(int head_dim, int B, int H, int Tq, int Tk, int causal, int dist_penalty, float p_drop) {
+    if (head_dim != 64 || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || causal || dist_penalty || !(p_drop < 1.f)) return 0;
+    if (((uint32_t)fminf(p_drop * 4294967296.f, 4294967295.f) >> 16) == 0) return 0;
+    if (g_s2t_opt_attn_v1 != 0 || Tq <= 64 || !(Tq >= 128 || (Tq >= S2T_ATTN_V2_MIN_TQ && Tk >= 128))) return 0;
+    if (!((unsigned long long)B * H * Tq * (unsigned long long)((Tk + 3) & ~3) < (1ull << 34))) return 0;
+    return (size_t)B * H * ((Tq + 127) / 128) * ((Tk + 63) / 64) * 256 * sizeof(uint32_t);
+}
+// what the forward needs beyond the shape to run attn_fwd2_kernel (its launch condition below); the backward asks the same question,
+// so that it reads a record only where the forward wrote one
+static bool keep_route(int dtype, int head_dim, const AttnArgs& a) {
+    return dtype == S2T_BF16 && s2t_attn_keep_bytes(head_dim, a.B, a.H, a.Tq, a.Tk, a.causal, a.dist_pen, a.p_drop) > 0 &&
+           (a.o_st % 4) == 0 && (a.o_sb % 4) == 0 && ((uintptr_t)a.O & 7) == 0 && span32(a.k_st, a.Tk) && span32(a.v_st, a.Tk) &&
+           ((uintptr_t)a.keep & 3) == 0;
+}
+
+static int attn_fwd_impl(int dtype, int head_dim, int B, int H, int Tq, int Tk,
                             const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
                             const void* V, long v_st, long v_sb, void* O, long o_st, long o_sb, float* LSE,
                             const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
-                            void* stream) {
+                            void* keep, void* stream) {
     AttnArgs a{};
+    a.keep = static_cast<uint32_t*>(keep);
     a.dist_pen = dist_penalty;
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.LSE = LSE;
     a.q_st = q_st; a.q_sb = q_sb; a.k_st = k_st; a.k_sb = k_sb; a.v_st = v_st; a.v_sb = v_sb; a.o_st = o_st; a.o_sb = o_sb;
@@ -1693,6 +1804,7 @@ extern "C" int s2t_attn_fwd(int dtype, int head_dim, int B, int H, int Tq, int T
     if (!Q || !K || !V || !O) return S2T_EINVAL;
     const long s[] = {q_st, q_sb, k_st, k_sb, v_st, v_sb};
     if (!strides_ok(dtype, s, 6)) return S2T_EINVAL;
+    if (a.keep && !keep_route(dtype, head_dim, a)) return S2T_ENOTSUP;        // no kernel of this call would write the record
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("attn_fwd", st, 4.0 * B * H * (double)Tq * Tk * head_dim * (causal ? 0.5 : 1.0), 0.0);
     if (dtype == S2T_BF16 && head_dim == 64 && sq_fwd_route(a)) {
@@ -1703,24 +1815,43 @@ extern "C" int s2t_attn_fwd(int dtype, int head_dim, int B, int H, int Tq, int T
     if (dtype == S2T_BF16 && head_dim == 64 && (Tq >= 128 || (Tq >= S2T_ATTN_V2_MIN_TQ && Tk >= 128)) && (o_st % 4) == 0 && (o_sb % 4) == 0 && ((uintptr_t)O & 7) == 0) {
         const bool v1 = g_s2t_opt_attn_v1 != 0 || !span32(k_st, Tk) || !span32(v_st, Tk);     // s2t_set_option("attn_v1")
         if (!v1) {
-            hipLaunchKernelGGL(attn_fwd2_kernel, dim3((Tq + 127) / 128, H, B), dim3(256), 32768 + 512 + 16384, st, a);
+            if (a.keep) hipLaunchKernelGGL(attn_fwd2_kernel<true>, dim3((Tq + 127) / 128, H, B), dim3(256), 32768 + 512 + 16384, st, a);
+            else hipLaunchKernelGGL(attn_fwd2_kernel<false>, dim3((Tq + 127) / 128, H, B), dim3(256), 32768 + 512 + 16384, st, a);
             S2T_LAUNCH_CHECK();
             return S2T_OK;
         }
     }
+    if (a.keep) return S2T_ENOTSUP;                    // not reached: keep_route is the condition above
     if (dtype == S2T_BF16) return head_dim == 64 ? fwd_launch<bf16, 64>(a, st) : fwd_launch<bf16, 32>(a, st);
     return head_dim == 64 ? fwd_launch<float, 64>(a, st) : fwd_launch<float, 32>(a, st);
 }
+extern "C" int s2t_attn_fwd(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+                            const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
+                            const void* V, long v_st, long v_sb, void* O, long o_st, long o_sb, float* LSE,
+                            const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
+                            void* stream) {
+    return attn_fwd_impl(dtype, head_dim, B, H, Tq, Tk, Q, q_st, q_sb, K, k_st, k_sb, V, v_st, v_sb, O, o_st, o_sb, LSE, klen, causal, dist_penalty,
+                         scale, p_drop, seed, nullptr, stream);
+}
+extern "C" int s2t_attn_fwd_keep(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+                                 const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
+                                 const void* V, long v_st, long v_sb, void* O, long o_st, long o_sb, float* LSE,
+                                 const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
+                                 void* keep, void* stream) {
+    return attn_fwd_impl(dtype, head_dim, B, H, Tq, Tk, Q, q_st, q_sb, K, k_st, k_sb, V, v_st, v_sb, O, o_st, o_sb, LSE, klen, causal, dist_penalty,
+                         scale, p_drop, seed, keep, stream);
+}
 
-extern "C" int s2t_attn_bwd(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+static int attn_bwd_impl(int dtype, int head_dim, int B, int H, int Tq, int Tk,
                             const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
                             const void* V, long v_st, long v_sb, const void* O, long o_st, long o_sb,
                             const void* dO, long do_st, long do_sb, const float* LSE, float* Delta,
                             void* dQ, long dq_st, long dq_sb, void* dK, long dk_st, long dk_sb,
                             void* dV, long dv_st, long dv_sb,
                             const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
-                            void* stream) {
+                            const void* keep, void* stream) {
     AttnArgs a{};
+    a.keep = static_cast<uint32_t*>(const_cast<void*>(keep));
     a.dist_pen = dist_penalty;
     a.Q = Q; a.K = K; a.V = V; a.O = const_cast<void*>(O); a.LSE = const_cast<float*>(LSE);
     a.dO = dO; a.dQ = dQ; a.dK = dK; a.dV = dV; a.Delta = Delta;
@@ -1733,6 +1864,7 @@ extern "C" int s2t_attn_bwd(int dtype, int head_dim, int B, int H, int Tq, int T
     if (!Q || !K || !V || !O || !dO || !LSE || !Delta || !dQ || !dK || !dV) return S2T_EINVAL;
     const long s[] = {q_st, q_sb, k_st, k_sb, v_st, v_sb, do_st, do_sb};
     if (!strides_ok(dtype, s, 8)) return S2T_EINVAL;
+    if (a.keep && !keep_route(dtype, head_dim, a)) return S2T_ENOTSUP;        // the forward of this call wrote no record
     hipStream_t st = (hipStream_t)stream;
     // issued FLOPs: the two-kernel routes make S and dP twice (14 B H Tq Tk d), the one-pass short-query route once (10).  bench.py
     // rescales this family by 10 / 14 on the assumption of two recomputations, so the figure it reports for the short-query route is
@@ -1741,6 +1873,28 @@ extern "C" int s2t_attn_bwd(int dtype, int head_dim, int B, int H, int Tq, int T
     ProfScope prof("attn_bwd", st, (sq ? 10.0 : 14.0) * B * H * (double)Tq * Tk * head_dim * (causal ? 0.5 : 1.0), 0.0);
     if (dtype == S2T_BF16) return head_dim == 64 ? bwd_launch<bf16, 64>(a, st) : bwd_launch<bf16, 32>(a, st);
     return head_dim == 64 ? bwd_launch<float, 64>(a, st) : bwd_launch<float, 32>(a, st);
+}
+extern "C" int s2t_attn_bwd(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+                            const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
+                            const void* V, long v_st, long v_sb, const void* O, long o_st, long o_sb,
+                            const void* dO, long do_st, long do_sb, const float* LSE, float* Delta,
+                            void* dQ, long dq_st, long dq_sb, void* dK, long dk_st, long dk_sb,
+                            void* dV, long dv_st, long dv_sb,
+                            const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
+                            void* stream) {
+    return attn_bwd_impl(dtype, head_dim, B, H, Tq, Tk, Q, q_st, q_sb, K, k_st, k_sb, V, v_st, v_sb, O, o_st, o_sb, dO, do_st, do_sb, LSE, Delta,
+                         dQ, dq_st, dq_sb, dK, dk_st, dk_sb, dV, dv_st, dv_sb, klen, causal, dist_penalty, scale, p_drop, seed, nullptr, stream);
+}
+extern "C" int s2t_attn_bwd_keep(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+                                 const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
+                                 const void* V, long v_st, long v_sb, const void* O, long o_st, long o_sb,
+                                 const void* dO, long do_st, long do_sb, const float* LSE, float* Delta,
+                                 void* dQ, long dq_st, long dq_sb, void* dK, long dk_st, long dk_sb,
+                                 void* dV, long dv_st, long dv_sb,
+                                 const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
+                                 const void* keep, void* stream) {
+    return attn_bwd_impl(dtype, head_dim, B, H, Tq, Tk, Q, q_st, q_sb, K, k_st, k_sb, V, v_st, v_sb, O, o_st, o_sb, dO, do_st, do_sb, LSE, Delta,
+                         dQ, dq_st, dq_sb, dK, dk_st, dk_sb, dV, dv_st, dv_sb, klen, causal, dist_penalty, scale, p_drop, seed, keep, stream);
 }
 
 // ------------------------------------------------------------------------------------ head-averaged attention probabilities

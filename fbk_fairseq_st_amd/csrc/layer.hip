@@ -16,6 +16,7 @@ struct Ws {
     size_t h1, st1, qkv, ctx, lse, y1;                    // self-attention block (y1 = its output = input of the next block)
     size_t h2, st2, q, kv, ctx2, lse2, y2;                // encoder-attention block (decoder)
     size_t h3, st3, a, pre, amask;                        // FFN
+    size_t keep, nkeep;                                   // self-attention's dropout keep-bit record (training; 0 bytes = the backward hashes)
     size_t total, nmask;
 };
 Ws layout(const S2TLayerDesc& L, int training) {
@@ -33,6 +34,9 @@ Ws layout(const S2TLayerDesc& L, int training) {
     if (L.gelu) w.pre = take(M * (size_t)L.ffn * e);
     w.nmask = (training && !L.gelu) ? s2t_gemm_relu_mask_bytes((int)M, L.ffn, L.D) : 0;
     if (w.nmask) w.amask = take(w.nmask);
+    // the attention forward's dropout decisions, one bit each, for the two backward kernels that would hash them again
+    w.nkeep = (training && L.p_attn > 0.f) ? s2t_attn_keep_bytes(L.D / L.heads, L.B, L.heads, L.T, L.T, L.causal, L.dist_penalty, L.p_attn) : 0;
+    if (w.nkeep) w.keep = take(w.nkeep);
     w.total = o;
     return w;
 }
@@ -97,8 +101,13 @@ extern "C" int s2t_layer_fwd(const S2TLayerDesc* Lp, S2TLayerCall* c, void* st) 
     TRY(linear(L, M, 3 * D, D, ws + w.h1, L.w_qkv, L.b_qkv, ws + w.qkv, nullptr, nullptr, nullptr, 0, S2T_ACT_NONE, 0.f, 0, st));
     const char* qkv = ws + w.qkv;
     const long ts3 = (long)L.B * 3 * D, bs3 = 3 * D, ts1 = (long)L.B * D, bs1 = D;
-    TRY(s2t_attn_fwd(L.dtype, d, L.B, H, L.T, L.T, qkv, ts3, bs3, qkv + (size_t)D * 2, ts3, bs3, qkv + (size_t)2 * D * 2, ts3, bs3, ws + w.ctx, ts1, bs1,
-                     reinterpret_cast<float*>(ws + w.lse), c->self_klen, L.causal, L.dist_penalty, scale, pa, c->seed_sa_attn, st));
+    if (w.nkeep) {
+        TRY(s2t_attn_fwd_keep(L.dtype, d, L.B, H, L.T, L.T, qkv, ts3, bs3, qkv + (size_t)D * 2, ts3, bs3, qkv + (size_t)2 * D * 2, ts3, bs3, ws + w.ctx, ts1, bs1,
+                              reinterpret_cast<float*>(ws + w.lse), c->self_klen, L.causal, L.dist_penalty, scale, pa, c->seed_sa_attn, ws + w.keep, st));
+    } else {
+        TRY(s2t_attn_fwd(L.dtype, d, L.B, H, L.T, L.T, qkv, ts3, bs3, qkv + (size_t)D * 2, ts3, bs3, qkv + (size_t)2 * D * 2, ts3, bs3, ws + w.ctx, ts1, bs1,
+                         reinterpret_cast<float*>(ws + w.lse), c->self_klen, L.causal, L.dist_penalty, scale, pa, c->seed_sa_attn, st));
+    }
     TRY(linear(L, M, D, D, ws + w.ctx, L.w_o, L.b_o, ws + w.y1, c->x, nullptr, nullptr, 0, S2T_ACT_NONE, p, c->seed_sa_out, st));
     const char* xin = ws + w.y1;
     // ---- encoder-attention block (decoder layer)                           (transformer_layer.py:324-352)
@@ -194,10 +203,17 @@ extern "C" int s2t_layer_bwd(const S2TLayerDesc* Lp, S2TLayerCall* c, void* st) 
     TRY(linear_dx(L, M, D, D, dcur_d, L.w_o, tm + t.dctx, nullptr, 0, S2T_ACT_NONE, 1.f, 0, st));
     const char* qkv = ws + w.qkv;
     char* dqkv = tm + t.dqkv;
-    TRY(s2t_attn_bwd(L.dtype, d, L.B, H, L.T, L.T, qkv, ts3, bs3, qkv + (size_t)D * 2, ts3, bs3, qkv + (size_t)2 * D * 2, ts3, bs3, ws + w.ctx, ts1, bs1,
-                     tm + t.dctx, ts1, bs1, reinterpret_cast<const float*>(ws + w.lse), reinterpret_cast<float*>(tm + t.delta),
-                     dqkv, ts3, bs3, dqkv + (size_t)D * 2, ts3, bs3, dqkv + (size_t)2 * D * 2, ts3, bs3, c->self_klen, L.causal, L.dist_penalty, scale, pa,
-                     c->seed_sa_attn, st));
+    if (w.nkeep) {
+        TRY(s2t_attn_bwd_keep(L.dtype, d, L.B, H, L.T, L.T, qkv, ts3, bs3, qkv + (size_t)D * 2, ts3, bs3, qkv + (size_t)2 * D * 2, ts3, bs3, ws + w.ctx, ts1, bs1,
+                              tm + t.dctx, ts1, bs1, reinterpret_cast<const float*>(ws + w.lse), reinterpret_cast<float*>(tm + t.delta),
+                              dqkv, ts3, bs3, dqkv + (size_t)D * 2, ts3, bs3, dqkv + (size_t)2 * D * 2, ts3, bs3, c->self_klen, L.causal, L.dist_penalty, scale, pa,
+                              c->seed_sa_attn, ws + w.keep, st));
+    } else {
+        TRY(s2t_attn_bwd(L.dtype, d, L.B, H, L.T, L.T, qkv, ts3, bs3, qkv + (size_t)D * 2, ts3, bs3, qkv + (size_t)2 * D * 2, ts3, bs3, ws + w.ctx, ts1, bs1,
+                         tm + t.dctx, ts1, bs1, reinterpret_cast<const float*>(ws + w.lse), reinterpret_cast<float*>(tm + t.delta),
+                         dqkv, ts3, bs3, dqkv + (size_t)D * 2, ts3, bs3, dqkv + (size_t)2 * D * 2, ts3, bs3, c->self_klen, L.causal, L.dist_penalty, scale, pa,
+                         c->seed_sa_attn, st));
+    }
     TRY(queue_dw(*c, dqkv, ws + w.h1, L.g_w_qkv, L.g_b_qkv, 3 * D, D, M));
     TRY(linear_dx(L, M, 3 * D, D, dqkv, L.w_qkv, tm + t.dh1, nullptr, 0, S2T_ACT_NONE, 1.f, 0, st));
     const float* st1 = reinterpret_cast<const float*>(ws + w.st1);

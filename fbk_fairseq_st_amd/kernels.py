@@ -182,6 +182,51 @@ def attn_fwd(q, k, v, heads, klen=None, causal=False, scale=None, p_drop=0.0, se
     return out, lse
 
 
+def attn_keep_bytes(d, B, heads, Tq, Tk, causal=False, dist_penalty=False, p_drop=0.0):
+    """Bytes of the dropout keep-bit record of a bf16 attention call (s2t_attn_keep_bytes: layout in include/s2t_hip.h); 0 = the call
+    does not take the second-generation kernels' plain path and its backward hashes.  Follows the attention route options."""
+    return int(_lib().s2t_attn_keep_bytes(d, B, heads, Tq, Tk, int(causal), int(bool(dist_penalty)), float(p_drop)))
+
+
+def attn_fwd_keep(q, k, v, heads, keep, klen=None, causal=False, scale=None, p_drop=0.0, seed=0, out=None, dist_penalty=False):
+    """attn_fwd that also writes the keep-bit record `keep` (a device tensor of attn_keep_bytes bytes; None = attn_fwd exactly)"""
+    Tq, B, D = q.shape
+    Tk = k.shape[0]
+    d = D // heads
+    if scale is None:
+        scale = d ** -0.5
+    if out is None:
+        out = torch.empty((Tq, B, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, heads, Tq), dtype=torch.float32, device=q.device)
+    if keep is not None:
+        L.require_cuda(keep)
+        assert keep.is_contiguous() and keep.numel() * keep.element_size() >= attn_keep_bytes(d, B, heads, Tq, Tk, causal, dist_penalty, p_drop)
+    rc = _lib().s2t_attn_fwd_keep(L.dt(q), d, B, heads, Tq, Tk, L.ptr(q), *_tb(q), L.ptr(k), *_tb(k), L.ptr(v), *_tb(v),
+                                  L.ptr(out), *_tb(out), L.ptr(lse), L.ptr(klen), int(causal), int(bool(dist_penalty)), float(scale),
+                                  float(p_drop), int(seed), L.ptr(keep), L.stream())
+    L.check(rc, "s2t_attn_fwd_keep")
+    return out, lse
+
+
+def attn_bwd_keep(q, k, v, o, do, lse, heads, dq, dk, dv, keep, klen=None, causal=False, scale=None, p_drop=0.0, seed=0, dist_penalty=False):
+    """attn_bwd reading the keep-bit record attn_fwd_keep wrote for this call (None = attn_bwd exactly)"""
+    Tq, B, D = q.shape
+    Tk = k.shape[0]
+    d = D // heads
+    if scale is None:
+        scale = d ** -0.5
+    delta = torch.empty((B, heads, Tq), dtype=torch.float32, device=q.device)
+    if keep is not None:
+        L.require_cuda(keep)
+        assert keep.is_contiguous() and keep.numel() * keep.element_size() >= attn_keep_bytes(d, B, heads, Tq, Tk, causal, dist_penalty, p_drop)
+    rc = _lib().s2t_attn_bwd_keep(L.dt(q), d, B, heads, Tq, Tk, L.ptr(q), *_tb(q), L.ptr(k), *_tb(k), L.ptr(v), *_tb(v),
+                                  L.ptr(o), *_tb(o), L.ptr(do), *_tb(do), L.ptr(lse), L.ptr(delta),
+                                  L.ptr(dq), *_tb(dq), L.ptr(dk), *_tb(dk), L.ptr(dv), *_tb(dv),
+                                  L.ptr(klen), int(causal), int(bool(dist_penalty)), float(scale), float(p_drop), int(seed), L.ptr(keep), L.stream())
+    L.check(rc, "s2t_attn_bwd_keep")
+    return dq, dk, dv
+
+
 def attn_probs_avg(q, k, heads, klen=None, scale=None, heads_used=None):
     """head-averaged attention probabilities of one layer, recomputed from q [Tq,B,D'] and k [Tk,B,D'] -> f32 [B, Tq, Tk]
     (transformer.py:756-782: what the decoder returns as `attn` for its alignment layer)"""

@@ -38,6 +38,10 @@ SIGNATURES = {
     "s2t_attn_fwd": [c_int] * 6 + [P, c_long, c_long] * 4 + [P, P, c_int, c_int, c_float, c_float, c_ull, P],
     "s2t_attn_bwd": [c_int] * 6 + [P, c_long, c_long] * 5 + [P, P] + [P, c_long, c_long] * 3 +
                     [P, c_int, c_int, c_float, c_float, c_ull, P],
+    "s2t_attn_keep_bytes": [c_int] * 7 + [c_float],             # returns size_t
+    "s2t_attn_fwd_keep": [c_int] * 6 + [P, c_long, c_long] * 4 + [P, P, c_int, c_int, c_float, c_float, c_ull, P, P],
+    "s2t_attn_bwd_keep": [c_int] * 6 + [P, c_long, c_long] * 5 + [P, P] + [P, c_long, c_long] * 3 +
+                         [P, c_int, c_int, c_float, c_float, c_ull, P, P],
     "s2t_attn_probs_avg": [c_int] * 6 + [P, c_long, c_long] * 2 + [P, c_int, c_float, P, P],
     "s2t_layernorm_fwd": [c_int, P, P, P, P, P, P, c_int, c_int, c_float, P],
     "s2t_layernorm_bwd": [c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, P, c_float, c_ull, P],
@@ -211,7 +215,7 @@ def build(verbose=False):
 # never built here): both call the same libs2t_hip.so, neither computes anything.
 FAST_PATH = os.path.join(_HERE, "_s2t_fastcall.so")
 _HOST_SIDE = ("s2t_host_batch_by_size", "s2t_host_ctc_uer")          # CPU work: release the GIL around the call, as ctypes does
-_SIZE_T_RESULT = ("s2t_gemm_relu_mask_bytes", "s2t_layer_ws_bytes", "s2t_layer_bwd_tmp_bytes", "s2t_decode_lds_bytes",
+_SIZE_T_RESULT = ("s2t_gemm_relu_mask_bytes", "s2t_attn_keep_bytes", "s2t_layer_ws_bytes", "s2t_layer_bwd_tmp_bytes", "s2t_decode_lds_bytes",
                   "s2t_ctc_loss_any_workspace")
 
 

@@ -170,8 +170,37 @@ int s2t_attn_bwd(int dtype, int head_dim, int B, int H, int Tq, int Tk,
                  const void* dO, long do_st, long do_sb, const float* LSE, float* Delta,
                  void* dQ, long dq_st, long dq_sb, void* dK, long dk_st, long dk_sb, void* dV, long dv_st, long dv_sb,
                  const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed, void* stream);
+/* Dropout keep-bit record: the forward writes the keep decision of every (query, key) pair, one bit each, and the backward reads
+ * them instead of hashing every pair again in each of its two kernels.  The decisions are the hash's own, so results are bit-equal
+ * to s2t_attn_fwd / s2t_attn_bwd.
+ * s2t_attn_keep_bytes = size of the record of a bf16 call of this shape, or 0 when the call would not run the second-generation
+ * kernels on their plain path: head_dim 64, no causal mask, no distance penalty, p_drop >= 2^-16, B H Tq ((Tk + 3) & ~3) < 2^34,
+ * Tq > 64 (not the short-query kernels, which hash once per pair as it is) and Tq >= 128 or (Tq >= "attn_v2_min_tq" and Tk >= 128),
+ * "attn_v1" off.  It follows those two options: ask again after s2t_set_option, and keep them fixed between a forward and its backward.
+ * Layout, in 32-bit words, with nq = ceil(Tq / 128) query blocks and nk = ceil(Tk / 64) key tiles:
+ *     word  (((b * H + h) * nq + bx) * nk + t) * 256 + 64 * w + lane          (w = 0..3, lane = 16 * q + r16, q = 0..3, r16 = 0..15)
+ *     bit   16 * qb + 4 * j + r  (qb = 0..1, j = 0..3, r = 0..3)  =  1 when the pair
+ *           query 128 * bx + 32 * w + 16 * qb + r16,  key 64 * t + 16 * j + 4 * q + r    is kept.
+ * Key tiles at or past klen[b] are not written; bits of queries >= Tq and of keys >= klen[b] mean nothing.
+ * s2t_attn_fwd_keep / s2t_attn_bwd_keep = s2t_attn_fwd / s2t_attn_bwd plus the record (4-byte aligned device memory of that size).
+ * keep = NULL is s2t_attn_fwd / s2t_attn_bwd exactly.  With a record, a call that s2t_attn_keep_bytes answers with 0, that is not
+ * bf16, or whose O / K / V layout leaves the second-generation forward (O strides % 4, O & 7, K / V rows beyond 32-bit offsets)
+ * gets S2T_ENOTSUP and launches nothing.  The backward must get the record its forward wrote (same shape, klen, p_drop, seed). */
+size_t s2t_attn_keep_bytes(int head_dim, int B, int H, int Tq, int Tk, int causal, int dist_penalty, float p_drop);
+int s2t_attn_fwd_keep(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+                      const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
+                      const void* V, long v_st, long v_sb, void* O, long o_st, long o_sb, float* LSE,
+                      const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
+                      void* keep, void* stream);
+int s2t_attn_bwd_keep(int dtype, int head_dim, int B, int H, int Tq, int Tk,
+                      const void* Q, long q_st, long q_sb, const void* K, long k_st, long k_sb,
+                      const void* V, long v_st, long v_sb, const void* O, long o_st, long o_sb,
+                      const void* dO, long do_st, long do_sb, const float* LSE, float* Delta,
+                      void* dQ, long dq_st, long dq_sb, void* dK, long dk_st, long dk_sb, void* dV, long dv_st, long dv_sb,
+                      const int* klen, int causal, int dist_penalty, float scale, float p_drop, unsigned long long seed,
+                      const void* keep, void* stream);
 
-/* ---- LayerNorm (fairseq/modules/layer_norm.py:29-32; eps 1e-5; rows of D <= 1024) ------------------ */
+/* ---- LayerNorm(fairseq/modules/layer_norm.py:29-32; eps 1e-5; rows of D <= 1024) ------------------ */
 int s2t_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y,
                       float* mean, float* rstd, int M, int D, float eps, void* stream);
 /* dx = LN'(dy) + dres (dres optional: the residual branch of a pre-LN block); dgamma/dbeta += (f32).
