@@ -684,6 +684,57 @@ def score_targets(logits_list, target):
     return out
 
 
+def _ctc_decode_args(logits, in_len, what):
+    if logits.dim() != 3 or logits.stride(-1) != 1:
+        raise ValueError("%s: logits must be [T, B, V] with unit column stride, got %s" % (what, tuple(logits.shape)))
+    T, B, V = logits.shape
+    if tuple(in_len.shape) != (B,) or in_len.dtype != torch.int32:
+        raise ValueError("%s: in_len must be int32 [%d], got %s %s" % (what, B, in_len.dtype, tuple(in_len.shape)))
+    return T, B, V, in_len.contiguous()
+
+
+def ctc_greedy(logits, in_len, blank):
+    """best-path CTC transcripts of logits [T, B, V] (time-major, any row stride >= V; include/s2t_hip.h s2t_ctc_greedy).  in_len:
+    int32 [B].  Returns device tensors (tokens int32 [B, T], n int32 [B], frames int32 [B, T, 2], tok_score f32 [B, T], score f32 [B]);
+    of a sentence's rows only the first n[b] entries are written."""
+    T, B, V, in_len = _ctc_decode_args(logits, in_len, "ctc_greedy")
+    dev = logits.device
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    n = torch.zeros((B,), dtype=torch.int32, device=dev)
+    frames = torch.empty((B, T, 2), dtype=torch.int32, device=dev)
+    tok_score = torch.empty((B, T), dtype=torch.float32, device=dev)
+    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    if T * B == 0:
+        return tokens, n, frames, tok_score, score
+    ws = torch.empty((int(_lib().s2t_ctc_greedy_workspace(T, B)),), dtype=torch.uint8, device=dev)
+    L.check(_lib().s2t_ctc_greedy(L.dt(logits), L.ptr(logits), L.ptr(in_len), L.ptr(ws), L.ptr(tokens), L.ptr(n), L.ptr(frames),
+                                  L.ptr(tok_score), L.ptr(score), T, B, V, _row_ld(logits), int(blank), L.stream()), "s2t_ctc_greedy")
+    return tokens, n, frames, tok_score, score
+
+
+def ctc_prefix_beam(logits, in_len, blank, beam, cand, nbest):
+    """CTC prefix beam search over logits [T, B, V] (include/s2t_hip.h s2t_ctc_prefix_beam): beam <= 16 live prefixes, the cand <= 16
+    best non-blank symbols per frame, the nbest <= beam best hypotheses out.  Returns device tensors (tokens int32 [B, nbest, T],
+    lens int32 [B, nbest], scores f32 [B, nbest], n_hyp int32 [B]), best first; a sentence may have fewer than nbest hypotheses."""
+    T, B, V, in_len = _ctc_decode_args(logits, in_len, "ctc_prefix_beam")
+    dev = logits.device
+    beam, cand, nbest = int(beam), int(cand), int(nbest)
+    tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=dev)
+    lens = torch.zeros((B, nbest), dtype=torch.int32, device=dev)
+    scores = torch.full((B, nbest), float("-inf"), dtype=torch.float32, device=dev)
+    n_hyp = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if T * B == 0:
+        if B:                                          # no frames: the empty hypothesis, score 0
+            n_hyp.fill_(1)
+            scores[:, 0] = 0
+        return tokens, lens, scores, n_hyp
+    ws = torch.empty((int(_lib().s2t_ctc_prefix_beam_workspace(T, B, beam, cand, nbest)),), dtype=torch.uint8, device=dev)
+    L.check(_lib().s2t_ctc_prefix_beam(L.dt(logits), L.ptr(logits), L.ptr(in_len), L.ptr(ws), L.ptr(tokens), L.ptr(lens), L.ptr(scores),
+                                       L.ptr(n_hyp), T, B, V, _row_ld(logits), int(blank), beam, cand, nbest, L.stream()),
+            "s2t_ctc_prefix_beam")
+    return tokens, lens, scores, n_hyp
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

@@ -338,6 +338,33 @@ int s2t_ctc_loss_any(int dtype, const void* logits, const long long* targets, co
                      float* lse, void* ws, float* nll, void* grad, float* loss_sum,
                      int T, int B, int V, int ld, int Lmax, int blank, float grad_scale, int phase, const float* grad_scale_dev,
                      void* stream);
+/* ---- CTC decoding (csrc/ctc_decode.hip): transcripts from CTC logits [T][B][V] (f32 / bf16, row stride ld >= V), frames
+ * t >= in_len[b] (int32 [B], clamped to [0, T]) never reach a result, arithmetic in f32.  Per row x with m = max x, a = the FIRST
+ * index of that maximum and R = sum_{v != a} exp(x_v - m):   lp_v = (x_v - m) - log1p(R)   (the log-softmax, exact near 0).
+ * Common refusals, before anything is launched or written: S2T_OK at once for T*B <= 0; S2T_EINVAL for a NULL pointer, ld < V,
+ * V < 2, blank outside [0, V), beam / cand / nbest < 1, nbest > beam; S2T_ENOTSUP for a dtype other than f32 / bf16, beam > 16,
+ * cand > 16, cand > V - 1.  No atomics, no host read: a row phase (one wave per row) then one wave per sentence.
+ *
+ * Greedy (best path): pred_t = a of frame t; runs of equal predictions collapse, blank runs drop (`a _ a` two tokens, `a a` one).
+ * tokens [B][T] int32 (the first n_tok[b] written), frames [B][T][2] int32 = (first frame, one past the last frame) of each
+ * token's run, tok_score [B][T] f32 = sum of lp_pred over that run, score [B] = the same sum over all in_len[b] frames (blank
+ * frames included).  ws: s2t_ctc_greedy_workspace(T, B) = 8*T*B bytes. */
+size_t s2t_ctc_greedy_workspace(int T, int B);
+int s2t_ctc_greedy(int dtype, const void* logits, const int* in_len, void* ws, int* tokens, int* n_tok, int* frames,
+                   float* tok_score, float* score, int T, int B, int V, int ld, int blank, void* stream);
+/* Prefix beam search without a language model (Hannun et al. 2014), natural-log space.  State: at most `beam` prefixes (token
+ * strings) with pb / pnb = log-probability of the alignments of the frames so far that end in blank / non-blank; start
+ * {(): pb 0, pnb -inf}.  Per frame, C = the `cand` non-blank symbols of highest logit (ties: lower index), tot = pb (+) pnb,
+ * (+) = logaddexp:   new[p].pb (+)= lp_blank + tot;   c in C, c == last(p): new[p].pnb (+)= lp_c + pnb, new[p+c].pnb (+)= lp_c + pb;
+ * c in C, c != last(p): new[p+c].pnb (+)= lp_c + tot.  A prefix is its token STRING (64-bit hash + length): the extension of p and
+ * the updates of a live p+c meet in one entry, wherever p came from.  Entries of total -inf are no prefixes; the `beam` highest
+ * totals survive.  Output, best first: tokens [B][nbest][T] int32, lens [B][nbest], scores [B][nbest] f32 (lens 0 / scores -inf
+ * behind the n_hyp[b] <= nbest hypotheses that exist); in_len[b] == 0: the empty hypothesis, score 0.
+ * ws: s2t_ctc_prefix_beam_workspace(T, B, beam, cand, nbest) = 4*T*B*(2*beam + 2*cand + 1) bytes rounded up to 256 (the trie of
+ * (parent, token) nodes, then the rows' candidates). */
+size_t s2t_ctc_prefix_beam_workspace(int T, int B, int beam, int cand, int nbest);
+int s2t_ctc_prefix_beam(int dtype, const void* logits, const int* in_len, void* ws, int* tokens, int* lens, float* scores,
+                        int* n_hyp, int T, int B, int V, int ld, int blank, int beam, int cand, int nbest, void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
