@@ -13,36 +13,13 @@
 // pruned and re-created from its own parent while p+c stayed live.  The strings themselves live in a trie of (parent, token) nodes
 // in the workspace, at most T*beam per sentence, read back once at the end.
 #include "common.hpp"
+#include "ctc_rows.hpp"
 #include "s2t_hip.h"
 
 namespace {
 
 constexpr int CTCD_MAX_BEAM = 16, CTCD_MAX_CAND = 16;
 constexpr int CTCD_SLOTS = (CTCD_MAX_BEAM * (CTCD_MAX_CAND + 1) + 63) / 64;        // candidate entries per lane: 272 over 64 lanes
-
-// f(value, column) for every column of a row, lane `lane` of the wave taking the 16-byte vectors lane, lane + 64, ... and the
-// scalar tail (V % (16 / sizeof(T)), or the whole row when it does not start 16-byte aligned)
-template <typename T, typename F>
-__device__ __forceinline__ void row_for_each(const T* __restrict__ x, int V, int lane, F f) {
-    constexpr int E = 16 / (int)sizeof(T);
-    const int nv = (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? V / E : 0;
-    for (int c = lane; c < nv; c += 64) {
-        T v[E];
-        *reinterpret_cast<u32x4*>(v) = *reinterpret_cast<const u32x4*>(x + c * E);
-#pragma unroll
-        for (int e = 0; e < E; ++e) f(to_f32(v[e]), c * E + e);
-    }
-    for (int j = nv * E + lane; j < V; j += 64) f(to_f32(x[j]), j);
-}
-
-// (value, column) of the wave's best: the higher value, among equal values the lower column; column INT_MAX = none
-__device__ __forceinline__ void wave_best(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(i, o);
-        if (oi != 0x7fffffff && (i == 0x7fffffff || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
-    }
-}
 
 // ------------------------------------------------------------------ row phase
 // arg / arg_lp [T*B]: first index of the row's maximum and its log-probability (greedy; may be NULL);

@@ -735,6 +735,48 @@ def ctc_prefix_beam(logits, in_len, blank, beam, cand, nbest):
     return tokens, lens, scores, n_hyp
 
 
+CTC_ALIGN_MAX_TARGET = 4095       # S2T_CTC_ALIGN_MAX_TARGET of include/s2t_hip.h
+
+
+def ctc_align(logits, in_len, targets, tgt_len, blank):
+    """forced CTC alignment of the transcripts `targets` (int64 [B, Lmax], the first tgt_len[b] entries of a row; tgt_len int64 [B]) to
+    logits [T, B, V] (time-major, any row stride >= V; in_len int32 [B]): include/s2t_hip.h s2t_ctc_align states the rule.  Returns
+    device tensors (states int32 [B, T], frames int32 [B, Lmax, 2], tok_score f32 [B, Lmax], score f32 [B], status int32 [B]);
+    entries behind a transcript's length are not written."""
+    T, B, V, in_len = _ctc_decode_args(logits, in_len, "ctc_align")
+    if targets.dim() != 2 or targets.shape[0] != B or targets.dtype != torch.int64:
+        raise ValueError("ctc_align: targets must be int64 [%d, Lmax], got %s %s" % (B, targets.dtype, tuple(targets.shape)))
+    if tuple(tgt_len.shape) != (B,) or tgt_len.dtype != torch.int64:
+        raise ValueError("ctc_align: tgt_len must be int64 [%d], got %s %s" % (B, tgt_len.dtype, tuple(tgt_len.shape)))
+    Lmax = targets.shape[1]
+    if Lmax > CTC_ALIGN_MAX_TARGET:
+        raise ValueError("ctc_align: transcripts of at most %d tokens (S2T_CTC_ALIGN_MAX_TARGET), got a padded width of %d"
+                         % (CTC_ALIGN_MAX_TARGET, Lmax))
+    dev = logits.device
+    targets, tgt_len = targets.contiguous(), tgt_len.contiguous()
+    states = torch.full((B, T), -1, dtype=torch.int32, device=dev)
+    frames = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    tok_score = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if T * B == 0:
+        if B:                                          # no frames: only the empty transcript has a path
+            status.copy_((tgt_len != 0).to(torch.int32) + ((tgt_len < 0) | (tgt_len > Lmax)).to(torch.int32))
+            score.masked_fill_(status != 0, float("-inf"))
+            own = (torch.arange(Lmax, device=dev)[None, :] < tgt_len[:, None]) & (status == 1)[:, None]
+            frames[own] = -1
+            tok_score[own] = float("-inf")
+        return states, frames, tok_score, score, status
+    ws = torch.empty((int(_lib().s2t_ctc_align_workspace(T, B, Lmax)),), dtype=torch.uint8, device=dev)
+    # Lmax = 0: three empty tensors have no address, the entry point refuses NULL; nothing of them is read or written
+    pad = torch.empty((2,), dtype=torch.int64, device=dev) if Lmax == 0 else None
+    p = lambda t: L.ptr(t if Lmax else pad)
+    L.check(_lib().s2t_ctc_align(L.dt(logits), L.ptr(logits), L.ptr(in_len), p(targets), L.ptr(tgt_len), L.ptr(ws), L.ptr(states),
+                                 p(frames), p(tok_score), L.ptr(score), L.ptr(status), T, B, V, _row_ld(logits), Lmax, int(blank),
+                                 L.stream()), "s2t_ctc_align")
+    return states, frames, tok_score, score, status
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

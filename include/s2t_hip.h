@@ -365,6 +365,35 @@ int s2t_ctc_greedy(int dtype, const void* logits, const int* in_len, void* ws, i
 size_t s2t_ctc_prefix_beam_workspace(int T, int B, int beam, int cand, int nbest);
 int s2t_ctc_prefix_beam(int dtype, const void* logits, const int* in_len, void* ws, int* tokens, int* lens, float* scores,
                         int* n_hyp, int T, int B, int V, int ld, int blank, int beam, int cand, int nbest, void* stream);
+/* ---- CTC forced alignment (csrc/ctc_align.hip): the most likely CTC path among those that collapse to a GIVEN transcript.
+ * logits, in_len, lp_v, blank as in the CTC decoding section above (n = in_len[b] clamped to [0, T]); targets int64 [B][Lmax] and
+ * tgt_len int64 [B] as s2t_ctc_loss takes them.  For a sentence of L = tgt_len[b] tokens y the extended sequence has S = 2L + 1
+ * states, z_s = blank for even s and y[(s-1)/2] for odd s.  v[0][0] = lp_0[blank], v[0][1] = lp_0[y_0], every other state -inf;
+ * for t >= 1   v[t][s] = lp_t[z_s] + max over the allowed predecessors   s;  s-1 if s >= 1;  s-2 if s is odd, s >= 3 and
+ * y[(s-1)/2] != y[(s-3)/2].  Among equal values the HIGHER predecessor state wins (stay over advance over skip).  The path ends at
+ * frame n-1 in the better of S-1 and S-2, on equal values in S-1; for L = 0 in state 0.  All arithmetic in f32, no atomics; a
+ * sentence's result does not depend on B or on its place in the batch.
+ * status [B] int32: 0 aligned (n = 0 with L = 0: score 0);  1 infeasible: the best end value is -inf (too few frames for the
+ * tokens plus the blanks that repeated tokens force, n = 0 with L > 0, a needed column -inf on every frame);  2 tgt_len[b] outside
+ * [0, Lmax], or one of the first L tokens outside [0, V) or equal to the blank (nothing outside the row is read for it).
+ * states [B][T] int32: the state of every frame t < n; -1 for t >= n and for the whole row when status != 0.
+ * frames [B][Lmax][2] int32: (first frame, one past the last frame) of token i, the convention of s2t_ctc_greedy's frames.
+ * tok_score [B][Lmax] f32: the sum of lp over the token's frames.  score [B] f32: the sum over all n frames, blank frames
+ * included; -inf when status != 0.  Entries i >= L of frames / tok_score are not written; for status != 0 the first L are
+ * (-1, -1) / -inf, and when L itself is out of range nothing is written to the two arrays.
+ * NaN logits: the path is unspecified; the call terminates and stays inside its buffers.
+ * Refusals, before anything is launched: S2T_OK at once for T*B <= 0; S2T_EINVAL for a NULL pointer, ld < V, V < 2, blank outside
+ * [0, V), Lmax < 0, T*B > 2^31 - 1; S2T_ENOTSUP for a dtype other than f32 / bf16 and for Lmax > S2T_CTC_ALIGN_MAX_TARGET.
+ * Two launches, no host read: a row phase (one wave per row writes the sentence's L + 1 emissions) and a sentence phase -- one wave
+ * per sentence with 1 to 16 states per lane in registers for 2*Lmax + 1 <= 1024, one 256-thread workgroup with two LDS rows above.
+ * ws: s2t_ctc_align_workspace(T, B, Lmax) = 4*T*B*(Lmax + 1 + W) bytes rounded up to 256, with W = 64 for 2*Lmax + 1 <= 1024 and
+ * ceil((2*Lmax + 1) / 16) above (the emissions [T*B][Lmax + 1] f32, then W dwords of 2-bit back-pointers per sentence and frame);
+ * 0 for an empty problem or an Lmax out of range. */
+#define S2T_CTC_ALIGN_MAX_TARGET 4095
+size_t s2t_ctc_align_workspace(int T, int B, int Lmax);
+int s2t_ctc_align(int dtype, const void* logits, const int* in_len, const long long* targets, const long long* tgt_len, void* ws,
+                  int* states, int* frames, float* tok_score, float* score, int* status, int T, int B, int V, int ld, int Lmax,
+                  int blank, void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
