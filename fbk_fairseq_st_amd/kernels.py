@@ -777,6 +777,56 @@ def ctc_align(logits, in_len, targets, tgt_len, blank):
     return states, frames, tok_score, score, status
 
 
+EDIT_MAX_A = 32767                # S2T_EDIT_MAX_A of include/s2t_hip.h
+EDIT_MAX_B = 4095                 # S2T_EDIT_MAX_B
+
+
+def edit_align(a, a_len, b, b_len, costs=(1, 1, 1), collapse_blank=None, want_ops=False):
+    """edit-distance alignment of the token rows a [B, Amax] (first a_len[b] entries) to b [B, Bmax] (first b_len[b]) under the
+    integer costs (substitution, `a` token left alone, `b` token left alone): include/s2t_hip.h s2t_edit_align states the rule.
+    Tokens int32 or int64 per side, a side's lengths in its tokens' dtype.  collapse_blank: a's rows are per-frame labels, collapsed
+    (repeats, then that blank) in the same call.  Returns device tensors (counts int32 [B, 4] = matches, substitutions, b tokens left
+    alone, a tokens left alone; cost int32 [B]; status int32 [B], 0 done / 2 refused; a_n int32 [B], the rows of each alignment;
+    a_out [B, Amax] the collapsed tokens in a's dtype or None; ops uint8 [B, Amax + Bmax] and n_ops int32 [B], or None, None).
+    counts, cost, a_n and n_ops of a refused sentence are 0; entries of ops behind n_ops and of a_out behind a_n are not written."""
+    ints = (torch.int32, torch.int64)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0] or a.dtype not in ints or b.dtype not in ints:
+        raise ValueError("edit_align: a and b must be int32 / int64 [B, width] with one B, got %s %s and %s %s"
+                         % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    B, Amax, Bmax = a.shape[0], a.shape[1], b.shape[1]
+    if tuple(a_len.shape) != (B,) or a_len.dtype != a.dtype or tuple(b_len.shape) != (B,) or b_len.dtype != b.dtype:
+        raise ValueError("edit_align: a_len / b_len must be [%d] in the dtype of their tokens, got %s %s and %s %s"
+                         % (B, a_len.dtype, tuple(a_len.shape), b_len.dtype, tuple(b_len.shape)))
+    if Amax > EDIT_MAX_A or Bmax > EDIT_MAX_B:
+        raise ValueError("edit_align: padded widths of at most %d (S2T_EDIT_MAX_A) and %d (S2T_EDIT_MAX_B), got %d and %d"
+                         % (EDIT_MAX_A, EDIT_MAX_B, Amax, Bmax))
+    cs, ca, cb = (int(c) for c in costs)
+    if not all(1 <= c <= 255 for c in (cs, ca, cb)):
+        raise ValueError("edit_align: costs must be integers in [1, 255], got %r" % (tuple(costs),))
+    dev = a.device
+    collapse = collapse_blank is not None
+    counts = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+    cost = torch.zeros((B,), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    a_n = torch.zeros((B,), dtype=torch.int32, device=dev)
+    a_out = torch.empty((B, Amax), dtype=a.dtype, device=dev) if collapse else None
+    ops = torch.empty((B, Amax + Bmax), dtype=torch.uint8, device=dev) if want_ops else None
+    n_ops = torch.zeros((B,), dtype=torch.int32, device=dev) if want_ops else None
+    if B == 0:
+        return counts, cost, status, a_n, a_out, ops, n_ops
+    a, a_len, b, b_len = a.contiguous(), a_len.contiguous(), b.contiguous(), b_len.contiguous()
+    nbytes = int(_lib().s2t_edit_align_workspace(B, Amax, Bmax, 1)) if want_ops else 0
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read or written
+    pad = torch.empty((2,), dtype=torch.int64, device=dev)
+    p = lambda t: L.ptr(t if t.numel() else pad)
+    L.check(_lib().s2t_edit_align(p(a), L.ptr(a_len), a.element_size(), p(b), L.ptr(b_len), b.element_size(), B, Amax, Bmax, cs, ca, cb,
+                                  int(collapse), int(collapse_blank) if collapse else 0, L.ptr(ws), L.ptr(counts), L.ptr(cost),
+                                  L.ptr(status), L.ptr(a_n), p(a_out) if collapse else 0, p(ops) if want_ops else 0,
+                                  L.ptr(n_ops) if want_ops else 0, L.stream()), "s2t_edit_align")
+    return counts, cost, status, a_n, a_out, ops, n_ops
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

@@ -394,6 +394,62 @@ size_t s2t_ctc_align_workspace(int T, int B, int Lmax);
 int s2t_ctc_align(int dtype, const void* logits, const int* in_len, const long long* targets, const long long* tgt_len, void* ws,
                   int* states, int* frames, float* tok_score, float* score, int* status, int T, int B, int V, int ld, int Lmax,
                   int blank, void* stream);
+/* ---- Edit-distance alignment of token sequences (csrc/edit_align.hip): cost, step counts and optionally the path, per sentence.
+ * One sentence is a pair `a` (n tokens, the rows) and `b` (m tokens, the columns).  The three integer costs `cs`, `ca`, `cb`, each
+ * in [1, 255], price a substitution, an `a` token left alone, and a `b` token left alone.
+ * Recursion:
+ *   - D[0][0] = 0.
+ *   - D[0][j] = D[0][j-1] + cb (step B).
+ *   - D[i][0] = D[i-1][0] + ca (step A).
+ *   - Otherwise best = D[i-1][j-1] + (a[i-1] == b[j-1] ? 0 : cs), which is step M (match) or step S (substitution).
+ *   - Then, if D[i][j-1] + cb < best, take step B.
+ *   - Then, if D[i-1][j] + ca < best, take step A.
+ *   - Both comparisons are strict and are made in that order.
+ *   - This is exactly wer_utils.EditDistance(False).align and align_errors in runtime.hip.  The preference is diagonal first,
+ *     then left, then up.
+ * Path and outputs:
+ *   - The path is the one the chosen steps give from (n, m) back to (0, 0).
+ *   - counts[b] = (M, S, B, A) are the numbers of each step on that path.
+ *   - cost[b] = D[n][m].
+ *   - With `a` the decoded transcript, `b` the target and costs (4, 3, 3), S + B + A is the reference's compute_ctc_uer error
+ *     count for the sentence.
+ *   - Note that a minimum-cost path under (4, 3, 3) is not always a minimum-count path, so the counts must come from this path
+ *     and no other.
+ * Collapse mode:
+ *   - A flag makes a row of `a` a row of per-frame labels with a_len[b] frames.
+ *   - Repeats are collapsed, then `blank` is dropped, as s2t_host_ctc_uer does, in the same call.
+ *   - n is the number of survivors.
+ *   - The call writes n to a_n [B] and, when the pointer is given, the collapsed tokens to a_out [B][Amax].
+ * Optional path output:
+ *   - With ops != NULL, ops [B][Amax + Bmax] (uint8) gets the step codes in forward order: 0 for M, 1 for S, 2 for B, 3 for A.
+ *   - n_ops [B] gets the path's length.
+ *   - Entries behind it are not written.
+ * Status and limits:
+ *   - status [B] is 0 for done and 2 for refused.  A sentence is refused when its length lies outside [0, padded width].  Nothing
+ *     else is written for that sentence, counts and cost included.
+ *   - A sentence's result does not depend on B or on its place in the batch.
+ *   - No atomics and no host read.
+ *   - Padded widths are Bmax <= S2T_EDIT_MAX_B = 4095 and Amax <= S2T_EDIT_MAX_A = 32767.
+ *   - Tokens are int32 or int64, chosen per side by an element-size argument (a_elem, b_elem: 4 or 8).
+ * Operands: a [B][Amax] and a_len [B] have a_elem bytes per element, b [B][Bmax] and b_len [B] have b_elem (what s2t_ctc_greedy and
+ * s2t_ctc_argmax give is int32, the criterion's targets are int64); tokens compare as 64-bit integers.  counts [B][4], cost [B],
+ * status [B], a_n [B], n_ops [B] are int32; a_out has a's element size.  Without collapse mode `blank` is ignored, a_out is not
+ * touched, and a_n (optional) gets a_len[b].  a_n is required in collapse mode, n_ops with ops.
+ * One launch: one wave per sentence with 1 to 16 columns per lane in registers and the rows skewed across the lanes for
+ * Bmax + 1 <= 1024, one 256-thread workgroup with the same skew above.  A cell carries its cost and the four counts of its path,
+ * so no matrix is stored unless ops is asked for.
+ * ws: s2t_edit_align_workspace(B, Amax, Bmax, want_ops) = 8*B*Amax bytes rounded up to 256 (room for the collapsed tokens when a_out
+ * is NULL in collapse mode) plus, with want_ops, 4*B*(Amax + 1)*ceil((Bmax + 1) / 16) bytes rounded up to 256 (one dword of 2-bit
+ * steps per row and 16 columns); 0 for B <= 0 or a width out of range.  ws may be NULL when neither part is used.
+ * Refusals, before anything is launched: S2T_OK at once for B <= 0; S2T_EINVAL for a NULL required pointer (a, a_len, b, b_len,
+ * counts, cost, status; a_n in collapse mode; n_ops with ops; ws when it is used), a cost outside [1, 255], a negative width, an
+ * element size other than 4 or 8; S2T_ENOTSUP for Amax > S2T_EDIT_MAX_A or Bmax > S2T_EDIT_MAX_B. */
+#define S2T_EDIT_MAX_A 32767
+#define S2T_EDIT_MAX_B 4095
+size_t s2t_edit_align_workspace(int B, int Amax, int Bmax, int want_ops);
+int s2t_edit_align(const void* a, const void* a_len, int a_elem, const void* b, const void* b_len, int b_elem, int B, int Amax,
+                   int Bmax, int cs, int ca, int cb, int collapse, long long blank, void* ws, int* counts, int* cost, int* status,
+                   int* a_n, void* a_out, unsigned char* ops, int* n_ops, void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
