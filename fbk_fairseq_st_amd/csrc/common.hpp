@@ -126,6 +126,7 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
 // Checked offline (tools/drop_hash_check.py, profiles/r02_drop_hash_check.txt): avalanche |P(flip) - 1/2| < 0.01 on all 64 output
 // bits for every input bit, chi-square of the 16-bit fields ~1.0, keep-bit correlations between neighbouring elements / rows < 1e-3,
 // per-row and per-column keep counts binomial.
+// The statement the tests hold these bits to is tests/dropout_ref.py (s2t_dropout bit for bit, every other site through s2t_dropout).
 __device__ __forceinline__ uint32_t drop_seed_key(uint64_t seed) { return mix32((uint32_t)seed * 0x9E3779B9u + 0x7F4A7C15u); }
 __device__ __forceinline__ uint32_t drop_high_mix(uint64_t seed, uint64_t quad) {
     const uint32_t hw = (uint32_t)(quad >> 32) + (uint32_t)(seed >> 32);

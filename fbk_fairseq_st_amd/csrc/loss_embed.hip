@@ -199,8 +199,9 @@ extern "C" int s2t_embed_bwd(int dtype, const long long* tokens, const void* dou
     return S2T_OK;
 }
 
-// ------------------------------------------------------------------ dropout (Philox, mask regenerated in backward)
-// y = x * keep/(1-p) with keep from (seed, element index); backward = the same call on the gradient.
+// ------------------------------------------------------------------ dropout (stateless hash, mask regenerated in backward)
+// y = x * keep/(1-p) with keep from (seed, element index), common.hpp dropout_keep; backward = the same call on the gradient.
+// tests/test_dropout_hash_gpu.py holds this kernel bit for bit to the host statement of the rule in tests/dropout_ref.py.
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, size_t n, float p, unsigned long long seed, int vec) {
     const uint32_t th = (uint32_t)fminf(p * 4294967296.f, 4294967295.f);

@@ -502,7 +502,16 @@ int s2t_act_bwd(int dtype, const void* dy, const void* y, void* out, size_t n, i
                 void* stream);
 /* y += x (merging the gradients of two consumers of one activation) */
 int s2t_add_inplace(int dtype, const void* x, void* y, size_t n, void* stream);
-/* y = x * keep/(1-p), mask from Philox(seed, index); the backward pass calls it again on the gradient */
+/* y = x * keep/(1-p) (one rounding to the type; a dropped element is +0), keep a stateless hash of (seed, element index); the backward
+ * pass calls it again on the gradient.  The rule every kernel's mask follows (tests/dropout_ref.py restates it; the tests hold to that):
+ *   seed key    ks = mix32(lo32(seed) * 0x9E3779B9 + 0x7F4A7C15),  mix32(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16
+ *   quad hash   q = index >> 2;  a = lo32(q) ^ ks;  a = bitrev(a + (a mod 2^24) * C) for C = 0x3C6EF2, 0x9E3778, then a += (a mod 2^24) * 0x85EBCA;
+ *               a ^= a >> 16;  x = a ^ hwm;  y = bitrev(x + ((x ^ 0x68E31DA4) mod 2^24) * 0xC2B2AE)   (all in 32 bits)
+ *   field order element 4q + f draws 16 bits: f0 = y.lo, f1 = y.hi, f2 = x.lo, f3 = x.hi
+ *   threshold   kept <=> field >= th16,  th16 = (uint32)min(p * 2^32, 2^32 - 1 as f32) >> 16, in f32: the rate is quantised to 1/65536
+ * Index bits >= 34 and seed bits >= 32 enter through one xor only: hw = hi32(q) + hi32(seed), hwm = hw ^ hw << 13 ^ hw >> 7 ^ hw << 27.  Masks
+ * that differ only there are correlated (seeds 5 and 2^32 + 5 agree on 79 % of the elements at p = 0.25 where independent masks agree on
+ * 62.5 %).  The package issues seeds below 2^32. */
 int s2t_dropout(int dtype, const void* x, void* y, size_t n, float p, unsigned long long seed, void* stream);
 
 /* ---- ConvAttention2D blocks of the front end (examples/speech_recognition/modules/conv_attention_2d.py:46-135,

@@ -73,15 +73,17 @@ def hash_mask(p, seed, B, H, Tq, Tk):
 _cache = {}
 
 
-def run_case(cid, p):
-    """inputs, both forwards and both backwards of a case, computed once and shared (nothing modifies them)"""
-    key = (cid, p)
+def run_case(cid, p, seed_high=0):
+    """inputs, both forwards and both backwards of a case, computed once and shared (nothing modifies them); `seed_high` goes into the
+    upper word of the case's dropout seed"""
+    key = (cid, p, seed_high)
     if key in _cache:
         return _cache[key]
     idx, (_, B, H, Tq, Tk, klen, has) = next((i, c) for i, c in enumerate(CASES) if c[0] == cid)
     seed = 1000 * (idx + 1) + int(100 * p)
     D = H * D_HEAD
     g = torch.Generator().manual_seed(seed)
+    seed |= seed_high << 32
     qkv = torch.randn(max(Tq, Tk), B, 3 * D, generator=g).to(BF).to(DEV)
     q, k, v = qkv[:Tq, :, :D], qkv[:Tk, :, D:2 * D], qkv[:Tk, :, 2 * D:]
     do = torch.randn(Tq, B, D, generator=g).to(BF).to(DEV)
@@ -152,6 +154,23 @@ def test_decoded_record_is_the_hash_mask(cid, p):
     assert abs(frac - (1 - p)) < 6 * (p * (1 - p) / n) ** 0.5, frac           # a mask of that rate, not a constant
     bad = (got != want) & valid
     assert not bool(bad.any()), (int(bad.sum()), n, bad.nonzero()[:4].tolist())
+
+
+def test_record_and_hashing_kernels_at_a_seed_above_32_bits():
+    """case h8_128x64 with the upper word of the dropout seed set: the forward's record is still s2t_dropout's mask at that seed, and
+    the hashing forward and backward (which take the upper word once per launch) still equal the record-reading ones bit for bit"""
+    cid, p = "h8_128x64", 0.1
+    c = run_case(cid, p, seed_high=5)
+    assert c["seed"] >> 32 == 5 and c["nbytes"] > 0
+    assert torch.equal(c["o_keep"], c["o"]) and torch.equal(c["lse_keep"], c["lse"])
+    for name, a, b in zip(("dQ", "dK", "dV"), c["grads_keep"], c["grads"]):
+        assert torch.equal(a, b), (name, float((a.float() - b.float()).abs().max()))
+    B, H, Tq, Tk = c["B"], c["H"], c["Tq"], c["Tk"]
+    got = decode(c["rec"], B, H, Tq, Tk)[:, :, :Tq, :Tk]
+    want = hash_mask(p, c["seed"], B, H, Tq, Tk)
+    assert not bool((got != want).any()), int((got != want).sum())
+    assert bool((got != hash_mask(p, c["seed"] & 0xFFFFFFFF, B, H, Tq, Tk)).any()), "the seed's upper word does not reach the record"
+    assert not torch.equal(c["o"], run_case(cid, p)["o"])
 
 
 @pytest.mark.parametrize("p", RATES)

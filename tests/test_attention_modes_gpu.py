@@ -309,7 +309,7 @@ class FarRows(Layout):
         return kf, vf
 
 
-def attn_case(dtype, d, H, B, Tq, Tk, klen, causal, scale, pen, what, layout=None, ratios=None):
+def attn_case(dtype, d, H, B, Tq, Tk, klen, causal, scale, pen, what, layout=None, ratios=None, drop_seed=77):
     """forward + backward element by element against float64, LSE with and without dropout, the dropout adjoint identity with
     its negative control, and (pen) the negative control of the penalty.  Returns the launch counts of the plain fwd + bwd."""
     layout = layout or Layout()
@@ -330,8 +330,8 @@ def attn_case(dtype, d, H, B, Tq, Tk, klen, causal, scale, pen, what, layout=Non
         Oref0, bO0 = o_bound(R0, dtype)
         assert bool(((heads(o, H) - Oref0).abs() > bO0).any()), what + ": outputs with the penalty pass the unpenalised O bound"
     # dropout: same LSE, and forward and backward drop the same pairs
-    seed = 77
-    g = torch.Generator().manual_seed(seed)
+    seed = drop_seed
+    g = torch.Generator().manual_seed(77)
     v2c = (torch.randn(v0.shape, generator=g) * 0.7).to(dtype).to(DEV)
     _, v2 = layout.kv(k0, v2c)
     o1, lse1 = K.attn_fwd(q, k, v, H, out=layout.out(q), p_drop=P_DROP, seed=seed, **kw)
@@ -516,6 +516,46 @@ def test_dropout_mask_causal(dtype, v1):
     with set_option("attn_v1", v1):
         m = extract_mask(dtype, d, H, B, Tq, Tk, P_DROP, seed, causal=True)
     assert bool((m == want).all()), "%d pairs differ from s2t_dropout's mask" % int((m != want).sum())
+
+
+HIGH_SEED = (5 << 32) | 7          # the seed is a 64-bit argument: its upper word must reach the hash in every kernel
+HIGH_SEED_CASES = [
+    # id, dtype, d, attn_v1, penalty, causal
+    ("f32_gen1", F32, 64, 0, False, False), ("bf16_gen1", BF, 64, 1, False, False), ("bf16_gen2_fast_index", BF, 64, 0, False, False),
+    ("bf16_gen2_general_index", BF, 64, 0, True, False), ("bf16_gen2_causal", BF, 64, 0, False, True), ("bf16_d32", BF, 32, 0, False, False),
+]
+
+
+@pytest.mark.parametrize("case", HIGH_SEED_CASES, ids=[c[0] for c in HIGH_SEED_CASES])
+def test_dropout_mask_seed_above_32_bits(case):
+    """the kernels take the seed's scramble and its upper word once per launch or tile (drop_seed_key / drop_high_mix) where s2t_dropout
+    takes them per quad: at a seed above 2^32 the extracted mask is still s2t_dropout's, and is not the mask of the seed's low word.
+    The shape of test_dropout_mask_causal, the smallest above"""
+    _, dtype, d, v1, pen, causal = case
+    B, H, Tq, Tk = 2, 2, 130, 130
+    ok = allowed_pairs(B, Tq, Tk, None, causal).expand(B, H, Tq, Tk)
+    want = expected_mask(B, H, Tq, Tk, P_DROP, HIGH_SEED) & ok
+    with set_option("attn_v1", v1):
+        m = extract_mask(dtype, d, H, B, Tq, Tk, P_DROP, HIGH_SEED, causal=causal, pen=pen)
+    assert bool((m == want).all()), "%d pairs differ from s2t_dropout's mask" % int((m != want).sum())
+    low = expected_mask(B, H, Tq, Tk, P_DROP, HIGH_SEED & 0xFFFFFFFF) & ok
+    assert not bool((m == low).all()), "the seed's upper word does not reach the mask"
+
+
+ADJOINT_HIGH_SEED = [
+    # id, dtype, d, attn_v1, Tq, Tk
+    ("f32_gen1", F32, 64, 0, 130, 130), ("bf16_gen1", BF, 64, 1, 130, 130), ("bf16_gen2", BF, 64, 0, 130, 130),
+    ("bf16_fwd2_dq2_with_gen1_dkv", BF, 64, 0, 200, 100), ("bf16_d32", BF, 32, 0, 65, 63),
+]
+
+
+@pytest.mark.parametrize("case", ADJOINT_HIGH_SEED, ids=[c[0] for c in ADJOINT_HIGH_SEED])
+def test_backward_drops_the_forwards_pairs_at_a_seed_above_32_bits(case):
+    """attn_case with the dropout seed above 2^32: dQ and dK/dV kernels of both generations take the upper word as the forward does
+    (the adjoint identity holds with the forward's seed and fails with another)"""
+    name, dtype, d, v1, Tq, Tk = case
+    with set_option("attn_v1", v1):
+        attn_case(dtype, d, 2, 2, Tq, Tk, None, False, d ** -0.5, False, "64-bit seed " + name, drop_seed=HIGH_SEED)
 
 
 # ------------------------------------------------------------------ 4. s2t_attn_probs_avg

@@ -257,7 +257,7 @@ def bwd_flop_factor(c, Tq, Tk, causal):
     return c["attn_bwd_flops"] / (B * H * Tq * Tk * D_HEAD * (0.5 if causal else 1.0))
 
 
-def run_case(Tq, Tk, ragged, causal, p, what, dist_penalty=False, sq=True):
+def run_case(Tq, Tk, ragged, causal, p, what, dist_penalty=False, sq=True, seed=SEED):
     """one forward + backward against float64; sq: whether the backward must have taken the short-query route"""
     q, k, v, do, v2, klen, R = case_inputs(Tq, Tk, ragged, causal, dist_penalty)
     kl = klen.to(DEV) if klen is not None else None
@@ -272,23 +272,23 @@ def run_case(Tq, Tk, ragged, causal, p, what, dist_penalty=False, sq=True):
             Oref0, bO0 = o_bound(case_inputs(Tq, Tk, ragged, causal, False)[6])
             assert bool(((heads(o) - Oref0).abs() > bO0).any()), what + ": outputs with the penalty pass the unpenalised O bound"
     else:
-        o, lse = K.attn_fwd(q, k, v, H, p_drop=p, seed=SEED, **kw)
-        o2, lse2 = K.attn_fwd(q, k, v2, H, p_drop=p, seed=SEED, **kw)
+        o, lse = K.attn_fwd(q, k, v, H, p_drop=p, seed=seed, **kw)
+        o2, lse2 = K.attn_fwd(q, k, v2, H, p_drop=p, seed=seed, **kw)
         assert_close(lse.unsqueeze(-1), R.lse, R.bL, what + " LSE with dropout")
         assert_close(lse2.unsqueeze(-1), R.lse, R.bL, what + " LSE with dropout (V2)")
         with launches() as c:
-            K.attn_fwd(q, k, v, H, p_drop=p, seed=SEED, **kw)
-            delta, dq, dk, dv = attn_bwd(q, k, v, o, do, lse, kl, causal, dist_penalty, p, SEED)
-        dv_other = attn_bwd(q, k, v, o, do, lse, kl, causal, dist_penalty, p, SEED + 1)[3]
+            K.attn_fwd(q, k, v, H, p_drop=p, seed=seed, **kw)
+            delta, dq, dk, dv = attn_bwd(q, k, v, o, do, lse, kl, causal, dist_penalty, p, seed)
+        dv_other = attn_bwd(q, k, v, o, do, lse, kl, causal, dist_penalty, p, seed + 1)[3]
         check_adjoint(R, do, o2, v2, dv, dv_other, p, what)
-        keep = expected_mask(Tq, Tk, p, SEED)
+        keep = expected_mask(Tq, Tk, p, seed)
         check_bwd(R, o, do, delta, dq, dk, dv, what + " p=%.1f" % p, keep, p)
     assert c["attn_fwd"] == 1 and c["attn_bwd"] == 1, c
     f = bwd_flop_factor(c, Tq, Tk, causal)
     assert abs(f - (10 if sq else 14)) < 1e-6, "%s: the backward reports %.3f B H Tq Tk d FLOPs: %s route expected" % (
         what, f, "the short-query" if sq else "a two-kernel")
     # determinism: the same call again, bit for bit
-    again = attn_bwd(q, k, v, o, do, lse, kl, causal, dist_penalty, p, SEED)
+    again = attn_bwd(q, k, v, o, do, lse, kl, causal, dist_penalty, p, seed)
     for name, a, b_ in zip(("Delta", "dQ", "dK", "dV"), (delta, dq, dk, dv), again):
         assert torch.equal(a, b_), what + ": two runs of the backward differ in " + name
     # rows of dK / dV from klen[b] to Tk are written, as exact zeros (module docstring)
@@ -364,6 +364,22 @@ def test_dropout_mask_is_the_first_generations_and_s2t_dropouts(case):
         old = extract_mask(Tq, Tk, P_DROP, SEED, klen, causal)
     assert bool((new == old).all()), "short-query and first-generation masks differ in %d pairs" % int((new != old).sum())
     assert bool((new == want).all()), "%d pairs differ from s2t_dropout's mask" % int((new != want).sum())
+
+
+HIGH_SEED = (5 << 32) | 7          # the seed is a 64-bit argument: its upper word must reach the hash
+
+
+@pytest.mark.parametrize("case", [(17, 131, False, False), (17, 17, False, True)], ids=["Tq17_Tk131", "Tq17_Tk17_causal"])
+def test_dropout_mask_and_backward_at_a_seed_above_32_bits(case):
+    """the two smallest mask cases at a seed whose upper word is set: attn_fwd_sq_kernel's extracted mask is s2t_dropout's at that seed
+    and not its low word's, and the one-pass backward drops the same pairs (run_case: element-wise against float64 with that mask)"""
+    Tq, Tk, ragged, causal = case
+    ok = allowed_pairs(Tq, Tk, None, causal).expand(B, H, Tq, Tk)
+    want = expected_mask(Tq, Tk, P_DROP, HIGH_SEED) & ok
+    new = extract_mask(Tq, Tk, P_DROP, HIGH_SEED, None, causal)
+    assert bool((new == want).all()), "%d pairs differ from s2t_dropout's mask" % int((new != want).sum())
+    assert not bool((new == (expected_mask(Tq, Tk, P_DROP, HIGH_SEED & 0xFFFFFFFF) & ok)).all()), "the seed's upper word does not reach the mask"
+    run_case(Tq, Tk, ragged, causal, P_DROP, "64-bit seed Tq%d Tk%d" % (Tq, Tk), seed=HIGH_SEED)
 
 
 def test_attn_v2_min_tq_above_tq_leaves_the_route():

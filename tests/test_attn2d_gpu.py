@@ -295,24 +295,42 @@ TIME_T = [1, 3, 63, 64, 65, 127, 128, 129, 375]
 def test_time_attention_against_fp64(dtype, Fq, T, p):
     """O, lse, delta, dq, dk, dv of the one-thread-per-frame kernels: key tiles of KT = 64 (full, ragged, single), query grids of
     128 (one, several), and with dropout the exact keep mask of the padded index (bh T + i) Tp + j, Tp = (T + 3) & ~3"""
-    B, seed = 2, 1000 + T
+    time_attention_case(dtype, Fq, T, p, 1000 + T)
+
+
+HIGH_SEED = (5 << 32) | 7          # a dropout seed whose upper word is set
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_time_and_frequency_attention_dropout_seed_above_32_bits(dtype):
+    """both attentions, forward and backward, at F = 10 with the upper word of the seed set: T = 65 for the time kernels (two key tiles,
+    the second with one key; T = 1 and 3 have too few pairs to tell masks apart) and T = 1 for the frequency kernels"""
+    time_attention_case(dtype, 10, 65, 0.3, 1000 + 65, HIGH_SEED)
+    frequency_attention_case(dtype, 10, 1, 0.3, 2000 + 1, HIGH_SEED)
+    assert not torch.equal(time_mask(2, 65, 0.3, HIGH_SEED), time_mask(2, 65, 0.3, HIGH_SEED & 0xFFFFFFFF))
+    assert not torch.equal(freq_mask(2, 10, 0.3, HIGH_SEED), freq_mask(2, 10, 0.3, HIGH_SEED & 0xFFFFFFFF))
+
+
+def time_attention_case(dtype, Fq, T, p, data_seed, drop_seed=None):
+    B, seed = 2, data_seed
     M = T * B * Fq
     qkv = make_qkv(B, T, Fq, dtype, seed=T * 7 + Fq)
     cat = rows(M, 8, dtype, fill=float("nan"))
+    drop_seed = seed if drop_seed is None else drop_seed
     with launches(["attn2d"]) as n:
-        lse = K.a2d_time_fwd(qkv, cat, B, T, Fq, p, seed)
+        lse = K.a2d_time_fwd(qkv, cat, B, T, Fq, p, drop_seed)
     assert n["attn2d"] == 1
     what = "time F=%d T=%d %s p=%g" % (Fq, T, dtype, p)
-    O, eO, lse_ref, e_lse = time_fwd_ref(qkv, lse, B, T, Fq, p, seed)
+    O, eO, lse_ref, e_lse = time_fwd_ref(qkv, lse, B, T, Fq, p, drop_seed)
     assert_close(lse, lse_ref, 2 * e_lse, what + " lse", "time_lse")
     assert_close(planes(cat, B, T, Fq, 0), O, out_bound(eO, O, dtype), what + " O", "time_fwd")
     assert torch.isnan(cat[:, H:].float()).all()                # the frequency half is not the time kernel's
     dcat = randn(M, 8, seed=seed + 1, dtype=dtype)
     dqkv = torch.zeros(M, 16, dtype=dtype, device=DEV)
     with launches(["attn2d"]) as n:
-        delta = K.a2d_time_bwd(qkv, cat, dcat, lse, dqkv, B, T, Fq, p, seed)
+        delta = K.a2d_time_bwd(qkv, cat, dcat, lse, dqkv, B, T, Fq, p, drop_seed)
     assert n["attn2d"] == 1
-    d_ref, e_d, dq, dk, dv = time_bwd_ref(qkv, cat, dcat, lse, B, T, Fq, p, seed)
+    d_ref, e_d, dq, dk, dv = time_bwd_ref(qkv, cat, dcat, lse, B, T, Fq, p, drop_seed)
     assert_close(delta, d_ref, 2 * e_d + 1e-300, what + " delta", "time_delta")
     for (ref, e), ch, nm in ((dq, 0, "dq"), (dk, H, "dk"), (dv, 2 * H, "dv")):
         assert_close(planes(dqkv, B, T, Fq, ch), ref, out_bound(e, ref, dtype), what + " " + nm, "time_" + nm)
@@ -326,21 +344,26 @@ def test_time_attention_against_fp64(dtype, Fq, T, p):
 @pytest.mark.parametrize("p", [0.0, 0.3])
 def test_frequency_attention_against_fp64(dtype, Fq, T, p):
     """A and the output; dq, dk, dv ADDED to a non-zero dqkv (what the time backward wrote), mask index (bh F + f1) F + f2"""
-    B, seed = 2, 2000 + T
+    frequency_attention_case(dtype, Fq, T, p, 2000 + T)
+
+
+def frequency_attention_case(dtype, Fq, T, p, data_seed, drop_seed=None):
+    B, seed = 2, data_seed
     M = T * B * Fq
     qkv = make_qkv(B, T, Fq, dtype, seed=T * 5 + Fq, scale=0.5)
     cat = rows(M, 8, dtype, fill=float("nan"))
-    A = K.a2d_freq_fwd(qkv, cat, B, T, Fq, p, seed)
+    drop_seed = seed if drop_seed is None else drop_seed
+    A = K.a2d_freq_fwd(qkv, cat, B, T, Fq, p, drop_seed)
     what = "freq F=%d T=%d %s p=%g" % (Fq, T, dtype, p)
-    A_ref, eA, out, e_out = freq_fwd_ref(qkv, A, B, T, Fq, p, seed)
+    A_ref, eA, out, e_out = freq_fwd_ref(qkv, A, B, T, Fq, p, drop_seed)
     assert_close(A, A_ref, 2 * eA, what + " A", "freq_A")
     assert_close(planes(cat, B, T, Fq, H), out, out_bound(e_out, out, dtype), what + " out", "freq_fwd")
     assert torch.isnan(cat[:, :H].float()).all()
     dcat = randn(M, 8, seed=seed + 1, dtype=dtype)
     d0 = randn(M, 16, seed=seed + 2, dtype=dtype)
     dqkv = d0.clone()
-    K.a2d_freq_bwd(qkv, dcat, A, dqkv, B, T, Fq, p, seed)
-    dq, dk, dv = freq_bwd_ref(qkv, dcat, A, B, T, Fq, p, seed)
+    K.a2d_freq_bwd(qkv, dcat, A, dqkv, B, T, Fq, p, drop_seed)
+    dq, dk, dv = freq_bwd_ref(qkv, dcat, A, B, T, Fq, p, drop_seed)
     for (d, e), ch, nm in ((dq, 0, "dq"), (dk, H, "dk"), (dv, 2 * H, "dv")):
         ref = planes(d0, B, T, Fq, ch) + d
         e = e + U * ref.abs()

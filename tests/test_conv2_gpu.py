@@ -349,6 +349,14 @@ def test_dgrad_half_dropped():
     assert 0.45 < float((dy != 0).float().mean()) < 0.55
 
 
+def test_dgrad_dropout_seed_above_32_bits():
+    """the same case at a seed whose upper 32 bits are set: the keep mask is K.dropout's at that seed, and not the one of its low word"""
+    seed = (5 << 32) | 7
+    ins, dy = run_dgrad(3, 7, 33, 0.5, seed, seed=20)
+    check_dgrad(ins, dy, 7, 33, "conv2_dgrad (3, 7, 33) p=0.5, 64-bit seed", 0.5, seed)
+    assert not torch.equal(dy != 0, K.dropout(torch.ones_like(dy), 0.5, seed & 0xFFFFFFFF) != 0)
+
+
 @pytest.mark.parametrize("p", [0.0, 0.1])
 def test_dgrad_stage_reuse(p):
     """(200, 30, 9): 200 x 8 = 1,600 units on 768 workgroups (conv2.hip:278): some do two iterations, some three (conv2.hip:214)"""

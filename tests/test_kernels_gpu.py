@@ -41,6 +41,7 @@ def tol(dtype):
 
 
 DTYPES = [torch.float32, torch.bfloat16]
+HIGH_SEED = (5 << 32) | 7          # a seed whose upper word is in use: every fused site must fold it where s2t_dropout does
 
 
 def rnd(*shape, dtype=torch.float32, seed=0, scale=1.0):
@@ -256,6 +257,18 @@ def test_layernorm(dtype, M, D):
 @pytest.mark.parametrize("M,D", [(333, 512), (1000, 256), (50, 1024), (21, 100)])
 def test_layernorm_bwd_second_output_is_the_consumers_dropout(dtype, M, D):
     """dx_drop of s2t_layernorm_bwd == s2t_dropout(dx, p, seed), bit for bit (same element index, same rounding)"""
+    layernorm_bwd_second_output(dtype, M, D, 4242)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,D", [(333, 512), (50, 1024), (21, 100)])
+def test_layernorm_bwd_second_output_seed_above_32_bits(dtype, M, D):
+    """the kernel's three forms (D = 512, the wide row, the per-element index of a D that is no multiple of the lane's share) at a seed
+    whose upper word is set"""
+    layernorm_bwd_second_output(dtype, M, D, HIGH_SEED)
+
+
+def layernorm_bwd_second_output(dtype, M, D, seed):
     x = rnd(M, D, dtype=dtype, seed=1, scale=2.0).to(DEV)
     g = (1 + 0.1 * rnd(D, seed=2)).to(DEV); b = (0.1 * rnd(D, seed=3)).to(DEV)
     dy = rnd(M, D, dtype=dtype, seed=4).to(DEV); dres = rnd(M, D, dtype=dtype, seed=5).to(DEV)
@@ -263,9 +276,9 @@ def test_layernorm_bwd_second_output_is_the_consumers_dropout(dtype, M, D):
     dg = torch.zeros(D, device=DEV); db = torch.zeros(D, device=DEV)
     dx0 = K.layernorm_bwd(dy, x, mean, rstd, g, dg, db, dres=dres)
     dg2 = torch.zeros(D, device=DEV); db2 = torch.zeros(D, device=DEV)
-    dx1, dxd = K.layernorm_bwd(dy, x, mean, rstd, g, dg2, db2, dres=dres, drop=(0.3, 4242))
+    dx1, dxd = K.layernorm_bwd(dy, x, mean, rstd, g, dg2, db2, dres=dres, drop=(0.3, seed))
     assert torch.equal(dx0, dx1)
-    assert torch.equal(dxd, K.dropout(dx0, 0.3, 4242))
+    assert torch.equal(dxd, K.dropout(dx0, 0.3, seed))
     kept = float((dxd != 0).float().mean())
     assert abs(kept - 0.7) < 0.03
 
@@ -870,6 +883,48 @@ def test_gemm256_is_deterministic_under_load():
 def test_gemm_relu_one_bit_record(M, N, K_, p_drop):
     """fc1 / fc2 of the FFN (transformer_layer.py:128-136) with the ReLU decision kept as one bit per activation: the forward product
     equals the ACT_RELU one bit for bit, and the data gradient through the record equals the one that re-reads the activations"""
+    relu_one_bit_record(M, N, K_, p_drop, 77)
+
+
+def test_gemm_relu_one_bit_record_seed_above_32_bits():
+    """the smallest of the shapes above with fc1's dropout at a seed whose upper word is set: the record route folds it as the ACT_RELU
+    route does, and both draw s2t_dropout's mask"""
+    a = relu_one_bit_record(6211, 1536, 512, 0.1, HIGH_SEED)
+    keep = K.dropout(torch.ones_like(a), 0.1, HIGH_SEED) != 0
+    assert bool(((a == 0) | keep).all()), "an output survived where s2t_dropout drops"
+    frac = float(((a > 0) & keep).float().sum() / keep.float().sum())
+    assert 0.4 < frac < 0.55, "about half of what s2t_dropout keeps passes the ReLU"
+    low = K.dropout(torch.ones_like(a), 0.1, HIGH_SEED & 0xFFFFFFFF) != 0
+    assert not bool(((a == 0) | low).all()), "the seed's upper word must move the mask"
+
+
+def test_gemm256_dropout_epilogues_seed_above_32_bits():
+    """gemm256 takes the seed's scramble and its upper word once per launch (gemm_tile.hpp): at seeds above 2^32 its masked epilogues
+    still equal the 128-wide route's bit for bit, and the mask is s2t_dropout's at that seed (the smallest of TURN_SHAPES)"""
+    M, N, K_ = 6211, 1536, 512
+    dt = torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(M + N + K_)
+    a = torch.randn(M, K_, device=DEV, generator=g).to(dt); w = (torch.randn(N, K_, device=DEV, generator=g) * K_ ** -0.5).to(dt)
+    b = torch.randn(N, device=DEV, generator=g); r = torch.randn(M, N, device=DEV, generator=g).to(dt)
+    calls = [lambda: K.gemm(a, w, bias=b, p_drop=0.25, seed=HIGH_SEED), lambda: K.gemm(a, w, bias=b, residual=r, p_drop=0.1, seed=HIGH_SEED + 1),
+             lambda: K.gemm(a, w, bias=b, act=K.ACT_RELU, p_drop=0.1, seed=(1 << 63) | 5)]
+    old = K.set_option("gemm256", 0)
+    try:
+        want = [fn() for fn in calls]
+        K.set_option("gemm256", 1)
+        got = [fn() for fn in calls]
+        plain = K.gemm(a, w, bias=b)
+    finally:
+        K.set_option("gemm256", old)
+    for i in range(3):
+        assert torch.equal(got[i], want[i]), "epilogue %d: %d of %d values differ from the 128-wide route" % (i, int((got[i] != want[i]).sum()), got[i].numel())
+    keep = K.dropout(torch.ones_like(plain), 0.25, HIGH_SEED) != 0
+    assert torch.equal(got[0] != 0, keep & (plain != 0))
+    low = K.dropout(torch.ones_like(plain), 0.25, HIGH_SEED & 0xFFFFFFFF) != 0
+    assert not torch.equal(got[0] != 0, low & (plain != 0)), "the seed's upper word must move the mask"
+
+
+def relu_one_bit_record(M, N, K_, p_drop, seed):
     dtype = torch.bfloat16
     nb = K.relu_mask_bytes(M, N, K_)
     assert nb > 0 and nb % 8192 == 0 and nb * 8 >= M * N
@@ -877,9 +932,9 @@ def test_gemm_relu_one_bit_record(M, N, K_, p_drop):
     x = torch.randn(M, K_, device=DEV, generator=g).to(dtype); w = (torch.randn(N, K_, device=DEV, generator=g) * K_ ** -0.5).to(dtype)
     b = torch.randn(N, device=DEV, generator=g) * 0.1
     dy = torch.randn(M, K_, device=DEV, generator=g).to(dtype); w2 = (torch.randn(K_, N, device=DEV, generator=g) * 0.05).to(dtype)
-    a_ref = K.gemm(x, w, bias=b, act=K.ACT_RELU, p_drop=p_drop, seed=77)
+    a_ref = K.gemm(x, w, bias=b, act=K.ACT_RELU, p_drop=p_drop, seed=seed)
     rec = torch.full((nb,), 0xA5, dtype=torch.uint8, device=DEV)
-    a = K.gemm(x, w, bias=b, act=K.ACT_RELU_MASK, aux_out=rec, p_drop=p_drop, seed=77)
+    a = K.gemm(x, w, bias=b, act=K.ACT_RELU_MASK, aux_out=rec, p_drop=p_drop, seed=seed)
     assert torch.equal(a, a_ref)
     frac = float((a > 0).float().mean())
     assert (0.4 if p_drop == 0 else 0.35) < frac < 0.55
@@ -888,6 +943,7 @@ def test_gemm_relu_one_bit_record(M, N, K_, p_drop):
     da = K.gemm(dy, w2, trans_b=True, act=K.ACT_RELU_BWD_MASK, aux=rec, alpha=alpha)
     assert torch.equal(da, da_ref)
     assert torch.equal(da != 0, (a > 0) & (K.gemm(dy, w2, trans_b=True, alpha=alpha) != 0))
+    return a
 
 
 def test_gemm_relu_one_bit_record_refused_where_the_kernel_does_not_run():
@@ -1208,18 +1264,33 @@ def test_attn2d_in_projection_weight_gradient_one_pass(dtype, B, T):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_dropout_fused_into_bn_apply_and_scattered_gemm_epilogue(dtype):
     """the fused forms produce the bits of the separate s2t_dropout pass over the same tensor"""
+    fused_bn_apply_and_scattered_gemm(dtype, 99, 7)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_dropout_fused_into_bn_apply_and_gemm_epilogue_seed_above_32_bits(dtype):
+    """the same at seeds whose upper 32 bits are set, and the dense epilogue (no map_c) beside the scattered one"""
+    fused_bn_apply_and_scattered_gemm(dtype, HIGH_SEED + 92, HIGH_SEED)
+    a = rnd(300, 128, dtype=dtype, seed=4).to(DEV); w = rnd(64, 128, dtype=dtype, seed=5, scale=0.2).to(DEV)
+    plain = K.gemm(a, w)
+    o1, ref = K.gemm(a, w, p_drop=0.3, seed=HIGH_SEED), K.dropout(plain, 0.3, HIGH_SEED)
+    assert torch.equal(o1 == 0, ref == 0)
+    assert not torch.equal(o1 == 0, K.dropout(plain, 0.3, HIGH_SEED & 0xFFFFFFFF) == 0), "the seed's upper word must move the mask"
+
+
+def fused_bn_apply_and_scattered_gemm(dtype, seed_bn, seed_gemm):
     C, P = 64, 4096
     y = rnd(P, C, dtype=dtype, seed=1).to(DEV)
     sc, sh = (1 + 0.1 * rnd(C, seed=2)).to(DEV), (0.1 * rnd(C, seed=3)).to(DEV)
-    assert torch.equal(K.bn_apply(y, sc, sh, 0.2, 99), K.dropout(K.bn_apply(y, sc, sh), 0.2, 99))
+    assert torch.equal(K.bn_apply(y, sc, sh, 0.2, seed_bn), K.dropout(K.bn_apply(y, sc, sh), 0.2, seed_bn))
     # scattered output rows (map_c): the mask index is the element index of the destination tensor
     M, Kd, rows_out = 300, 128, 700
     a = rnd(M, Kd, dtype=dtype, seed=4).to(DEV); w = rnd(C, Kd, dtype=dtype, seed=5, scale=0.2).to(DEV)
     perm = torch.randperm(rows_out, generator=torch.Generator().manual_seed(6))[:M].to(torch.int32).to(DEV)
     o1 = torch.zeros(rows_out, C, dtype=dtype, device=DEV); o2 = torch.zeros(rows_out, C, dtype=dtype, device=DEV)
-    K.gemm(a, w, map_c=perm, out=o1, p_drop=0.3, seed=7)
+    K.gemm(a, w, map_c=perm, out=o1, p_drop=0.3, seed=seed_gemm)
     K.gemm(a, w, map_c=perm, out=o2)
-    ref = K.dropout(o2, 0.3, 7)
+    ref = K.dropout(o2, 0.3, seed_gemm)
     assert torch.equal(o1 == 0, ref == 0)                       # the same mask ...
     if dtype == torch.float32:
         assert torch.equal(o1, ref)

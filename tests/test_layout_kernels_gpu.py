@@ -178,6 +178,26 @@ def test_add_pos(T, B, D, offset, dtype):
     assert_same_bits(xi, want, "add_pos in place")
 
 
+@pytest.mark.parametrize("offset", [False, True], ids=["aligned", "offset"])
+def test_add_pos_dropout_seed_above_32_bits(offset):
+    """T, B, D = 9, 5, 64 in bf16, the 16-byte and the element-wise form: the dropout mask is s2t_dropout's also at a seed whose upper
+    32 bits are set (the seed is a 64-bit argument; every other case here passes a small one)"""
+    T, B, D, p, seed = 9, 5, 64, 0.3, (5 << 32) | 7
+    def buf():
+        t = rnd(T * B * D + 1, dtype=BF, seed=5)[1:].view(T, B, D) if offset else rnd(T, B, D, dtype=BF, seed=5)
+        assert (t.data_ptr() % 16 != 0) == offset
+        return t
+    table = rnd(T + 3, D, seed=6)
+    ld = add_pos_lens(T, B).to(DEV)
+    plain = torch.empty(T, B, D, dtype=BF, device=DEV)
+    K.add_pos(buf(), table, ld, out=plain)
+    dropped = K.dropout(plain.clone(), p, seed)
+    assert not torch.equal(bits(dropped), bits(K.dropout(plain.clone(), p, seed & 0xFFFFFFFF))), "the seed's upper word must move the mask"
+    xi = buf()
+    K.add_pos(xi, table, ld, p_drop=p, seed=seed)
+    assert_same_bits(xi, dropped.cpu(), "add_pos with dropout, 64-bit seed")
+
+
 def test_add_pos_grid_stride():
     """T = 600, B = 32, D = 512 in bf16: 1,228,800 16-byte items > 4,096 x 256, the vector form's grid-stride loop takes a second trip;
     with dropout against K.dropout(K.add_pos(...))"""

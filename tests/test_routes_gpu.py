@@ -702,6 +702,18 @@ def test_layernorm_bwd_small_kernel_both_settings(M):
     assert_close(outs[1][0], a, ulp + 2 * outs[0][1], "ln_small 1 vs 0")
 
 
+def test_layernorm_bwd_small_kernel_both_settings_seed_above_32_bits():
+    """the second output's keep pattern under both settings at a seed whose upper word is set (M = 7: the smallest M above with
+    more than one row)"""
+    M, D = 7, 512
+    x = rnd(M, D, dtype=BF, seed=M, scale=2.0) + 0.5
+    gamma, beta = 1 + 0.1 * rnd(D, seed=2), 0.1 * rnd(D, seed=3)
+    dy, dres = rnd(M, D, dtype=BF, seed=4), rnd(M, D, dtype=BF, seed=5)
+    for s in (1, 0):
+        with set_option("ln_small", s):
+            ln_check(x, gamma, beta, dy, dres, (0.1, (5 << 32) | 7), "LN ln_small=%d M=%d, 64-bit seed" % (s, M))
+
+
 # ------------------------------------------------------------------ attention
 def attn_check(dtype, H, B, Tq, Tk, klen, causal, what):
     """O = softmax(scale q k^T) V per head, and its backward, against float64.

@@ -309,8 +309,20 @@ def inv_keep(p):
 def test_act_bwd_relu(dtype, p, n, lead):
     """act 1: exactly dy (dropped out and rescaled first when p > 0) where y > 0, else +0 -- y = +0, -0 and the smallest positive
     value of the type included; aligned tensors take the 16-byte path, views one element into an allocation the element-wise one"""
+    act_bwd_relu(dtype, p, n, lead, 1234 + n)
+
+
+HIGH_SEED = (5 << 32) | 7          # a seed whose upper word is in use
+
+
+@pytest.mark.parametrize("lead", [8, 1], ids=["aligned", "offset"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_act_bwd_relu_seed_above_32_bits(dtype, lead):
+    act_bwd_relu(dtype, 0.3, 1000, lead, HIGH_SEED)
+
+
+def act_bwd_relu(dtype, p, n, lead, seed):
     dy, y = act_inputs(n, dtype)
-    seed = 1234 + n
     (dyd, _), (yd, _), (out, ob) = place(dy, lead), place(y, lead), place(torch.full((n,), float("nan"), dtype=dtype), lead)
     assert raw_act_bwd(dyd, yd, out, 1, p, seed) == 0
     g = dy
@@ -366,8 +378,17 @@ def test_act_bwd_gelu(dtype, p, n, lead):
 
     Measured on MI355X (n = 2^20 + 3, the MEASURED lines), largest |error| / |g|: f32 yardstick 2.8e-07, kernel 1.8e-07 (p = 0) and
     1.7e-07 (p = 0.3), aligned and offset alike; bf16 yardstick 2.3e-07, kernel 4.4e-03 (the output's rounding to bf16)."""
+    act_bwd_gelu(dtype, p, n, lead, 4321 + n)
+
+
+@pytest.mark.parametrize("lead", [8, 1], ids=["aligned", "offset"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_act_bwd_gelu_seed_above_32_bits(dtype, lead):
+    act_bwd_gelu(dtype, 0.3, 1000, lead, HIGH_SEED)
+
+
+def act_bwd_gelu(dtype, p, n, lead, seed):
     dy, y = act_inputs(n, dtype)
-    seed = 4321 + n
     (dyd, _), (yd, _), (out, ob) = place(dy, lead), place(y, lead), place(torch.full((n,), float("nan"), dtype=dtype), lead)
     assert raw_act_bwd(dyd, yd, out, 2, p, seed) == 0
     g = dy
