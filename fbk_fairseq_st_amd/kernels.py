@@ -827,6 +827,51 @@ def edit_align(a, a_len, b, b_len, costs=(1, 1, 1), collapse_blank=None, want_op
     return counts, cost, status, a_n, a_out, ops, n_ops
 
 
+BLEU_MAX_LEN = 4095               # S2T_BLEU_MAX_LEN of include/s2t_hip.h
+BLEU_WAVE_LEN = 64                # S2T_BLEU_WAVE_LEN: hypotheses up to this padded width take one wave each, wider ones a workgroup
+BLEU_GROUP_LEN = 256              # S2T_BLEU_GROUP_LEN: of 256 threads up to this width, of 1,024 above
+
+
+def bleu_stats(hyp, hyp_len, ref, ref_len, pad, eos, unk=-1, ref_row=None):
+    """BLEU statistics of the token rows hyp [B, Hmax] (first hyp_len[b] entries) against ref [Rrows, Rmax] (first ref_len[r]):
+    include/s2t_hip.h s2t_bleu_stats states the rule (trim by pad / eos, clipped n-gram matches of the orders 1 to 4, a reference
+    `unk` never matches; unk < 0 switches that off).  Tokens int32 or int64 per side, a side's lengths in its tokens' dtype.
+    ref_row: int32 [B], sentence b is scored against row ref_row[b]; None scores row b (then Rrows must be B).  Returns device
+    tensors (stats int32 [B, 10] = reflen, predlen, match1, count1, ... match4, count4; status int32 [B], 0 done / 2 refused: a
+    length outside its padded width or a ref_row entry outside [0, Rrows), the stats are zeros)."""
+    ints = (torch.int32, torch.int64)
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.dtype not in ints or ref.dtype not in ints:
+        raise ValueError("bleu_stats: hyp and ref must be int32 / int64 [rows, width], got %s %s and %s %s"
+                         % (hyp.dtype, tuple(hyp.shape), ref.dtype, tuple(ref.shape)))
+    B, Hmax, Rrows, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[0], ref.shape[1]
+    if tuple(hyp_len.shape) != (B,) or hyp_len.dtype != hyp.dtype or tuple(ref_len.shape) != (Rrows,) or ref_len.dtype != ref.dtype:
+        raise ValueError("bleu_stats: hyp_len must be [%d] and ref_len [%d] in the dtype of their tokens, got %s %s and %s %s"
+                         % (B, Rrows, hyp_len.dtype, tuple(hyp_len.shape), ref_len.dtype, tuple(ref_len.shape)))
+    if ref_row is None:
+        if Rrows != B:
+            raise ValueError("bleu_stats: %d hypotheses and %d references need a ref_row map" % (B, Rrows))
+    elif tuple(ref_row.shape) != (B,) or ref_row.dtype != torch.int32:
+        raise ValueError("bleu_stats: ref_row must be int32 [%d], got %s %s" % (B, ref_row.dtype, tuple(ref_row.shape)))
+    if Hmax > BLEU_MAX_LEN or Rmax > BLEU_MAX_LEN:
+        raise ValueError("bleu_stats: padded widths of at most %d (S2T_BLEU_MAX_LEN), got %d and %d" % (BLEU_MAX_LEN, Hmax, Rmax))
+    pad, eos, unk = int(pad), int(eos), int(unk)
+    if pad == eos or (unk >= 0 and unk in (pad, eos)):
+        raise ValueError("bleu_stats: pad, eos and unk must be three different ids, got %d, %d and %d" % (pad, eos, unk))
+    dev = hyp.device
+    stats = torch.zeros((B, 10), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return stats, status
+    hyp, hyp_len, ref, ref_len = hyp.contiguous(), hyp_len.contiguous(), ref.contiguous(), ref_len.contiguous()
+    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read
+    fill = torch.zeros((2,), dtype=torch.int64, device=dev)
+    p = lambda t: L.ptr(t if t.numel() else fill)
+    L.check(_lib().s2t_bleu_stats(p(hyp), L.ptr(hyp_len), hyp.element_size(), p(ref), p(ref_len), ref.element_size(),
+                                  L.ptr(ref_row.contiguous()) if ref_row is not None else 0, B, Hmax, Rmax, Rrows, pad, eos, unk,
+                                  L.ptr(stats), L.ptr(status), L.stream()), "s2t_bleu_stats")
+    return stats, status
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

@@ -450,6 +450,44 @@ size_t s2t_edit_align_workspace(int B, int Amax, int Bmax, int want_ops);
 int s2t_edit_align(const void* a, const void* a_len, int a_elem, const void* b, const void* b_len, int b_elem, int B, int Amax,
                    int Bmax, int cs, int ca, int cb, int collapse, long long blank, void* ws, int* counts, int* cost, int* status,
                    int* a_n, void* a_out, unsigned char* ops, int* n_ops, void* stream);
+/* ---- BLEU n-gram statistics of token sequences (csrc/bleu_stats.hip): the ten numbers of the reference's bleu_add
+ * (clib/libbleu/libbleu.cpp, called per sentence by fairseq/bleu.py:Scorer.add), per sentence.
+ * One sentence is a pair `hyp` (hyp_len tokens) and `ref` (ref_len tokens), with three token ids `pad`, `eos`, `unk`.
+ * Trim, each side inside its given length:
+ *   - Leading `pad` tokens are dropped.
+ *   - Then trailing tokens equal to `eos` or `pad` are dropped, but never the first remaining token: a sentence that is only [eos]
+ *     keeps length 1 and its token is eos; [eos, eos, eos] becomes [eos].
+ *   - `pad` or `eos` in the interior are ordinary tokens.
+ *   - A side that is empty after the left trim has length 0 and all its numbers are 0.  The reference reads out of bounds there;
+ *     this is the one deviation.
+ * Totals: predlen and reflen are the trimmed lengths; for n = 1 .. 4, count_n = max(predlen - n + 1, 0).
+ * Matches:
+ *   - match_n = the sum over distinct n-grams g of min(occurrences of g in the trimmed hyp, occurrences of g in the trimmed ref).
+ *   - It is 0 when either side is shorter than n.
+ *   - A reference token equal to `unk` never matches anything (bleu.py:83-86 rewrites it to -999).  A hypothesis `unk` still
+ *     counts in count_n.  unk < 0 switches this off.
+ * Comparison: tokens are int32 or int64 per side (hyp_elem, ref_elem: 4 or 8; a side's lengths have its element size) and compare
+ * as 64-bit integers.  n-grams are compared token by token, not by hash: apart from a 64-bit FNV collision the result is the
+ * reference's.
+ * The kernel computes match_n position by position: hypothesis position i matches at order n iff the number of earlier hypothesis
+ * positions with the same n-gram is below the number of reference positions with it.  One launch, one sentence per workgroup, no
+ * atomics, no host read; a sentence's result does not depend on the batch around it.  One wave per sentence for
+ * Hmax <= S2T_BLEU_WAVE_LEN, one 256-thread workgroup up to S2T_BLEU_GROUP_LEN, one of 1,024 threads above; both padded widths
+ * up to S2T_BLEU_MAX_LEN.
+ * Outputs: stats [B][10] int32 in the order of the reference's BleuStat -- reflen, predlen, match1, count1, ... match4, count4;
+ * status [B] int32, 0 for done and 2 for refused.  A sentence is refused when a length lies outside [0, padded width] or its
+ * ref_row entry lies outside [0, Rrows); its stats are written as zeros.
+ * ref_row: NULL for identity (then Rrows must equal B); otherwise sentence b is scored against row ref_row[b] of ref [Rrows][Rmax]
+ * with length ref_len[ref_row[b]], so that an n-best list shares its reference without copies.
+ * Refusals, before anything is launched: S2T_OK at once for B <= 0; S2T_EINVAL for a NULL required pointer (hyp, hyp_len, ref,
+ * ref_len, stats, status), a negative width, an element size other than 4 or 8, Rrows != B without a map (Rrows < 0 with one),
+ * pad == eos, or unk >= 0 equal to pad or eos; S2T_ENOTSUP for a width above S2T_BLEU_MAX_LEN. */
+#define S2T_BLEU_MAX_LEN 4095
+#define S2T_BLEU_WAVE_LEN 64
+#define S2T_BLEU_GROUP_LEN 256
+int s2t_bleu_stats(const void* hyp, const void* hyp_len, int hyp_elem, const void* ref, const void* ref_len, int ref_elem,
+                   const int* ref_row, int B, int Hmax, int Rmax, int Rrows, long long pad, long long eos, long long unk,
+                   int* stats, int* status, void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
