@@ -872,6 +872,90 @@ def bleu_stats(hyp, hyp_len, ref, ref_len, pad, eos, unk=-1, ref_row=None):
     return stats, status
 
 
+FBANK_MAX_BINS = 128              # S2T_FBANK_MAX_BINS of include/s2t_hip.h
+FBANK_TILE_ELEMS = 8192           # S2T_FBANK_TILE_ELEMS: a workgroup takes FBANK_TILE_ELEMS // N consecutive frames
+FBANK_FFT_SIZES = (256, 512, 1024)
+
+
+def fbank_frame_tile(N):
+    """S2T_FBANK_FRAME_TILE(N): the frames one workgroup of s2t_fbank takes"""
+    return FBANK_TILE_ELEMS // N
+
+
+def fbank(waves, wave_len, window, twiddle, bank, weights, S, N, preemph=0.97, remove_dc=True):
+    """log-mel filterbanks of the rows of waves [B, Nmax] (int16 or float32, unit stride inside a row, any row stride; the first
+    wave_len[b] samples, wave_len int64 [B]): include/s2t_hip.h s2t_fbank states the rule.  window float32 [W], twiddle float64 [N],
+    bank int32 [F, 3] and weights float32 [n] are the host-built tables (fbank.FbankFrontEnd makes them); S the shift in samples,
+    N the FFT size.  Returns device tensors (out f32 [B, Tmax, F] with zeros behind a sentence's frames, out_len int32 [B], status
+    int32 [B]: 0 done / 1 no frames / 2 refused)."""
+    if waves.dim() != 2 or waves.dtype not in (torch.int16, torch.float32):
+        raise ValueError("fbank: waves must be int16 or float32 [B, Nmax], got %s %s" % (waves.dtype, tuple(waves.shape)))
+    B, Nmax = waves.shape
+    if tuple(wave_len.shape) != (B,) or wave_len.dtype != torch.int64:
+        raise ValueError("fbank: wave_len must be int64 [%d], got %s %s" % (B, wave_len.dtype, tuple(wave_len.shape)))
+    S, N = int(S), int(N)
+    if N not in FBANK_FFT_SIZES:
+        raise ValueError("fbank: FFT sizes %s, got %d" % (FBANK_FFT_SIZES, N))
+    if window.dim() != 1 or window.dtype != torch.float32 or not N // 2 < window.shape[0] <= N:
+        raise ValueError("fbank: window must be float32 [W] with %d < W <= %d, got %s %s" % (N // 2, N, window.dtype, tuple(window.shape)))
+    if tuple(twiddle.shape) != (N,) or twiddle.dtype != torch.float64:
+        raise ValueError("fbank: twiddle must be float64 [%d], got %s %s" % (N, twiddle.dtype, tuple(twiddle.shape)))
+    if bank.dim() != 2 or bank.shape[1] != 3 or bank.dtype != torch.int32 or not 1 <= bank.shape[0] <= FBANK_MAX_BINS:
+        raise ValueError("fbank: bank must be int32 [F, 3] with 1 <= F <= %d (S2T_FBANK_MAX_BINS), got %s %s"
+                         % (FBANK_MAX_BINS, bank.dtype, tuple(bank.shape)))
+    if weights.dim() != 1 or weights.dtype != torch.float32 or weights.shape[0] > N:
+        raise ValueError("fbank: weights must be float32 [n] with n <= %d, got %s %s" % (N, weights.dtype, tuple(weights.shape)))
+    if S < 1:
+        raise ValueError("fbank: a shift of at least one sample, got %d" % S)
+    preemph = float(preemph)
+    if not 0.0 <= preemph <= 1.0:
+        raise ValueError("fbank: preemphasis in [0, 1], got %r" % (preemph,))
+    W, F = window.shape[0], bank.shape[0]
+    Tmax = 0 if Nmax < W else 1 + (Nmax - W) // S
+    dev = waves.device
+    out = torch.empty((B, Tmax, F), dtype=torch.float32, device=dev)
+    out_len = torch.empty((B,), dtype=torch.int32, device=dev)       # both are written for every sentence
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, out_len, status
+    if Nmax > 1 and waves.stride(1) != 1:
+        waves = waves.contiguous()
+    row_stride = waves.stride(0) if B > 1 and Nmax else Nmax
+    if row_stride < 0:
+        waves, row_stride = waves.contiguous(), Nmax
+    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read or written
+    fill = torch.zeros((2,), dtype=torch.float32, device=dev)
+    p = lambda t: L.ptr(t if t.numel() else fill)
+    L.check(_lib().s2t_fbank(p(waves), waves.element_size(), row_stride, L.ptr(wave_len.contiguous()), B, Nmax, W, S, N, F, Tmax,
+                             L.ptr(window.contiguous()), L.ptr(twiddle.contiguous()), L.ptr(bank.contiguous()), p(weights.contiguous()),
+                             weights.shape[0], int(bool(remove_dc)), preemph, p(out), L.ptr(out_len), L.ptr(status), L.stream()),
+            "s2t_fbank")
+    return out, out_len, status
+
+
+def cmvn(x, lengths):
+    """per-utterance mean / variance normalisation of x [B, Tmax, F] (float32, contiguous) over its first lengths[b] rows (int32 or
+    int64 [B]), IN PLACE: include/s2t_hip.h s2t_cmvn states the rule.  Returns device tensors (out_len int32 [B], status int32 [B]:
+    0 done / 1 fewer than two rows / 2 refused); rows at or behind out_len[b] are zeros."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("cmvn: x must be a contiguous float32 [B, Tmax, F], got %s %s" % (x.dtype, tuple(x.shape)))
+    B, Tmax, F = x.shape
+    if tuple(lengths.shape) != (B,) or lengths.dtype not in (torch.int32, torch.int64):
+        raise ValueError("cmvn: lengths must be int32 / int64 [%d], got %s %s" % (B, lengths.dtype, tuple(lengths.shape)))
+    if not 1 <= F <= FBANK_MAX_BINS:
+        raise ValueError("cmvn: 1 to %d columns (S2T_FBANK_MAX_BINS), got %d" % (FBANK_MAX_BINS, F))
+    dev = x.device
+    out_len = torch.empty((B,), dtype=torch.int32, device=dev)       # both are written for every sentence
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out_len, status
+    lengths = lengths.contiguous()
+    fill = torch.zeros((2,), dtype=torch.float32, device=dev)      # Tmax = 0: nothing of x is read or written
+    L.check(_lib().s2t_cmvn(L.ptr(x if x.numel() else fill), L.ptr(lengths), lengths.element_size(), B, Tmax, F, L.ptr(out_len),
+                            L.ptr(status), L.stream()), "s2t_cmvn")
+    return out_len, status
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

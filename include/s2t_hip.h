@@ -488,6 +488,52 @@ int s2t_edit_align(const void* a, const void* a_len, int a_elem, const void* b, 
 int s2t_bleu_stats(const void* hyp, const void* hyp_len, int hyp_elem, const void* ref, const void* ref_len, int ref_elem,
                    const int* ref_row, int B, int Hmax, int Rmax, int Rrows, long long pad, long long eos, long long unk,
                    int* stats, int* status, void* stream);
+/* ---- Kaldi log-mel filterbanks of waveforms (csrc/fbank.hip): torchaudio.compliance.kaldi.fbank with its defaults, restated.
+ * Frames: W samples long, S apart, N the next power of two >= W.  An utterance of n samples has m = 0 frames if n < W, else
+ * m = 1 + (n - W) / S (snip-edges); frame t is the samples [t*S, t*S + W).  No sample at or behind n is read into a result.
+ * Per frame, in this order:
+ *   1. Samples become float: int16 at their integer value, unscaled; float32 as they are.
+ *   2. The frame's mean is subtracted (remove_dc).
+ *   3. Pre-emphasis with a replicated left edge: y[i] = x[i] - c*x[i-1] for i >= 1, y[0] = x[0] - c*x[0].
+ *   4. y is multiplied by `window` (W floats, built by the host: povey, hanning or hamming, symmetric).
+ *   5. Zero-padded to N.
+ *   6. Real FFT; the power re^2 + im^2 of the bins 0 .. N/2 - 1 (the Nyquist bin has weight 0 in every mel bin).
+ *   7. Mel energy e[j] = the sum over i < count_j of weights[offset_j + i] * power[first_j + i]: the bank in sparse form,
+ *      bank [F][3] int32 = (first_j, count_j, offset_j), weights [n_weights] float32, made in float64 and rounded once.
+ *   8. out[t][j] = log(max(e[j], 2^-23)).
+ * Tables: twiddle [N] float64 = cos(2 pi k / N) for k < N/2, then -sin(2 pi k / N) for k < N/2.  The kernel takes a half-size
+ * complex FFT of the packed frame (radix-2 Stockham in LDS) and splits it into even and odd parts; it calls no device sin / cos.
+ * Steps 2 to 7 run in float64 on the float samples of step 1 (csrc/fbank.hip says why); step 8 is float32.
+ * Whatever `bank` holds, a bin's range is cut to the powers and the weights there are.
+ * Operands: waves [B] rows of Nmax elements, row_stride elements apart (int16 for wave_elem 2, float32 for 4; no alignment beyond
+ * the element's), lengths int64 [B].  out [B][Tmax][F] float32 with Tmax the frames of Nmax samples; out_len [B], status [B] int32.
+ * Status: 0 done; 1 no features (0 frames); 2 refused (a length that is negative or above Nmax).  out_len is 0 unless done.  Every
+ * row of out at or behind out_len[b] is written as zeros; every row in front of it is written once: out needs no initialisation.
+ * One launch, no atomics, no host read.  A workgroup stages the samples of S2T_FBANK_TILE_ELEMS / N consecutive frames in LDS once
+ * (S2T_FBANK_FRAME_TILE); a result does not depend on the batch around it or on the tile its frame falls in.
+ * Refusals, before anything is launched, in this order: S2T_OK at once for B <= 0; S2T_EINVAL for a NULL pointer (every pointer
+ * but stream is required), wave_elem other than 2 or 4, Nmax < 0, row_stride < 0, W < 1, S < 1, F < 1, n_weights < 0, Tmax other
+ * than the frames of Nmax, preemph outside [0, 1]; then S2T_ENOTSUP for N other than 256, 512, 1024, W outside (N/2, N],
+ * F > S2T_FBANK_MAX_BINS, n_weights > N (a triangular bank has at most two bins over a power), B * tiles >= 2^31. */
+#define S2T_FBANK_MAX_BINS 128
+#define S2T_FBANK_TILE_ELEMS 8192
+#define S2T_FBANK_FRAME_TILE(N) (S2T_FBANK_TILE_ELEMS / (N))
+int s2t_fbank(const void* waves, int wave_elem, long long row_stride, const long long* lengths, int B, int Nmax, int W, int S,
+              int N, int F, int Tmax, const float* window, const double* twiddle, const int* bank, const float* weights,
+              int n_weights, int remove_dc, double preemph, float* out, int* out_len, int* status, void* stream);
+/* Per-utterance mean / variance normalisation (examples/speech_recognition/data/data_utils.py:9-25, apply_mv_norm), in place on
+ * x [B][Tmax][F] float32 over the first lengths[b] rows (lengths int32 or int64 by len_elem: 4 or 8), per column:
+ *   - mean is the column mean, var the unbiased variance;
+ *   - inv = 1/(sqrt(var) + 1e-8) for every column of the utterance if any of its columns has var < 1e-8, else 1/sqrt(var);
+ *   - x = (x - mean) * inv.
+ * The mean is summed over the differences from the utterance's first row and the variance over the differences from that mean,
+ * so a constant column has exactly its value as mean, exactly 0 as variance, and normalises to exactly 0.
+ * Status [B] int32: 0 done; 1 no features (fewer than 2 rows: one row has no variance, the reference yields NaN); 2 refused (a
+ * length that is negative or above Tmax).  out_len [B] int32 is the length if done, else 0; every row at or behind it is written as
+ * zeros.  One launch, one workgroup per utterance, no atomics, no host read.
+ * Refusals, before anything is launched, in this order: S2T_OK at once for B <= 0; S2T_EINVAL for a NULL pointer (x, lengths,
+ * out_len, status), len_elem other than 4 or 8, Tmax < 0, F < 1; then S2T_ENOTSUP for F > S2T_FBANK_MAX_BINS. */
+int s2t_cmvn(float* x, const void* lengths, int len_elem, int B, int Tmax, int F, int* out_len, int* status, void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
