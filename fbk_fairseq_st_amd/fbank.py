@@ -10,7 +10,8 @@ back to the host: lengths and statuses stay device tensors.
 The hot path is csrc/fbank.hip (kernels.fbank, kernels.cmvn; include/s2t_hip.h states both rules): one launch each.  The window
 and the sparse mel bank are built here in float64 and rounded once, the twiddles stay float64; all are cached per configuration and
 device.
-Not offered: dither, the energy column, snip_edges=False, VTLN, htk_compat, linear output, resampling.
+Not offered: dither, the energy column, snip_edges=False, VTLN, htk_compat, linear output.  Resampling to one of these rates, and
+speed perturbation, are resample.WaveResampler and resample.SpeedPerturb: their result is what `features` takes.
 """
 import math
 import wave

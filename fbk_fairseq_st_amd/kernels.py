@@ -956,6 +956,95 @@ def cmvn(x, lengths):
     return out_len, status
 
 
+RESAMPLE_MAX_BANKS = 8            # S2T_RESAMPLE_MAX_BANKS of include/s2t_hip.h: the banks of one call's table
+RESAMPLE_BANK_INTS = 7            # S2T_RESAMPLE_BANK_INTS: (in_unit, out_unit, taps, first_off, w_off, lo, extra)
+RESAMPLE_REUSE = 4                # S2T_RESAMPLE_REUSE: outputs of one phase a thread produces from one read of the weights
+RESAMPLE_TILE_ITEMS = 512         # S2T_RESAMPLE_TILE_ITEMS: (phase, unit group) pairs of a workgroup's tile
+RESAMPLE_MAX_PHASES = 512         # S2T_RESAMPLE_MAX_PHASES: out_unit
+RESAMPLE_MAX_BANK = 8192          # S2T_RESAMPLE_MAX_BANK: taps * out_unit, the weights of a bank
+RESAMPLE_MAX_SPAN = 7672          # S2T_RESAMPLE_MAX_SPAN: the samples a workgroup stages
+
+
+def resample_group(in_unit, out_unit, extra):
+    """the unit groups G of a workgroup's tile of s2t_resample for a bank (0: the bank does not fit)"""
+    if in_unit == out_unit:
+        return RESAMPLE_TILE_ITEMS
+    by_span = 0 if extra > RESAMPLE_MAX_SPAN else ((RESAMPLE_MAX_SPAN - extra) // in_unit + 1) // RESAMPLE_REUSE
+    return min(RESAMPLE_TILE_ITEMS // out_unit, by_span)
+
+
+def resample_tile(in_unit, out_unit, extra):
+    """the outputs of a workgroup's tile of s2t_resample for a bank"""
+    g = resample_group(in_unit, out_unit, extra)
+    return RESAMPLE_REUSE * g * (1 if in_unit == out_unit else out_unit)
+
+
+def resample_check_banks(banks, n_first, n_weights):
+    """the limits of s2t_resample on a table's banks (int32 [R, RESAMPLE_BANK_INTS], host), as ValueErrors"""
+    if banks.dim() != 2 or banks.shape[1] != RESAMPLE_BANK_INTS or banks.dtype != torch.int32 or banks.is_cuda or banks.shape[0] < 1:
+        raise ValueError("resample: banks must be a host int32 [R, %d] with R >= 1, got %s %s" % (RESAMPLE_BANK_INTS, banks.dtype, tuple(banks.shape)))
+    if banks.shape[0] > RESAMPLE_MAX_BANKS:
+        raise ValueError("resample: at most %d banks in a table (S2T_RESAMPLE_MAX_BANKS), got %d" % (RESAMPLE_MAX_BANKS, banks.shape[0]))
+    for r, (iu, ou, taps, f_off, w_off, lo, extra) in enumerate(banks.tolist()):
+        if iu < 1 or ou < 1:
+            raise ValueError("resample: bank %d: units of at least 1, got %d and %d" % (r, iu, ou))
+        if iu == ou:
+            continue
+        if taps < 1 or extra < taps or f_off < 0 or w_off < 0 or f_off + ou > n_first or w_off + taps * ou > n_weights or abs(lo) >= 1 << 30:
+            raise ValueError("resample: bank %d does not describe its tables: %r with %d firsts and %d weights"
+                             % (r, (iu, ou, taps, f_off, w_off, lo, extra), n_first, n_weights))
+        if ou > RESAMPLE_MAX_PHASES:
+            raise ValueError("resample: bank %d: %d phases, at most %d (S2T_RESAMPLE_MAX_PHASES)" % (r, ou, RESAMPLE_MAX_PHASES))
+        if taps * ou > RESAMPLE_MAX_BANK:
+            raise ValueError("resample: bank %d: %d weights (%d phases of %d taps), at most %d (S2T_RESAMPLE_MAX_BANK)"
+                             % (r, taps * ou, ou, taps, RESAMPLE_MAX_BANK))
+        if resample_group(iu, ou, extra) < 1:
+            raise ValueError("resample: bank %d: %d units span %d samples, at most %d are staged (S2T_RESAMPLE_MAX_SPAN)"
+                             % (r, RESAMPLE_REUSE, (RESAMPLE_REUSE - 1) * iu + extra, RESAMPLE_MAX_SPAN))
+
+
+def resample(waves, wave_len, banks, first, weights, Mmax, ratio_id=None):
+    """sinc resampling of the rows of waves [B, Nmax] (int16 or float32, unit stride inside a row, any row stride; the first
+    wave_len[b] samples, wave_len int32 or int64 [B]): include/s2t_hip.h s2t_resample states the rule.  banks is the HOST int32
+    [R, RESAMPLE_BANK_INTS] table, first int32 [n] and weights float32 [n] its device arrays (resample.pack_table makes them);
+    ratio_id int32 [B] picks a row's bank (None: bank 0); Mmax the width of the result.  Returns device tensors (out f32 [B, Mmax]
+    with zeros behind a row's samples, out_len int64 [B], status int32 [B]: 0 done / 1 no samples / 2 refused)."""
+    if waves.dim() != 2 or waves.dtype not in (torch.int16, torch.float32):
+        raise ValueError("resample: waves must be int16 or float32 [B, Nmax], got %s %s" % (waves.dtype, tuple(waves.shape)))
+    B, Nmax = waves.shape
+    if tuple(wave_len.shape) != (B,) or wave_len.dtype not in (torch.int32, torch.int64):
+        raise ValueError("resample: wave_len must be int32 / int64 [%d], got %s %s" % (B, wave_len.dtype, tuple(wave_len.shape)))
+    if ratio_id is not None and (tuple(ratio_id.shape) != (B,) or ratio_id.dtype != torch.int32):
+        raise ValueError("resample: ratio_id must be int32 [%d], got %s %s" % (B, ratio_id.dtype, tuple(ratio_id.shape)))
+    if first.dim() != 1 or first.dtype != torch.int32 or weights.dim() != 1 or weights.dtype != torch.float32:
+        raise ValueError("resample: first must be int32 [n] and weights float32 [n], got %s %s and %s %s"
+                         % (first.dtype, tuple(first.shape), weights.dtype, tuple(weights.shape)))
+    resample_check_banks(banks, first.shape[0], weights.shape[0])
+    Mmax = int(Mmax)
+    if not 0 <= Mmax < 1 << 31 or Nmax >= 1 << 31:
+        raise ValueError("resample: widths below 2^31, got Nmax %d and Mmax %d" % (Nmax, Mmax))
+    dev = waves.device
+    out = torch.empty((B, Mmax), dtype=torch.float32, device=dev)
+    out_len = torch.empty((B,), dtype=torch.int64, device=dev)       # both are written for every row
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, out_len, status
+    if Nmax > 1 and waves.stride(1) != 1:
+        waves = waves.contiguous()
+    row_stride = waves.stride(0) if B > 1 and Nmax else Nmax
+    if row_stride < 0:
+        waves, row_stride = waves.contiguous(), Nmax
+    banks = banks.contiguous()
+    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read or written
+    fill = torch.zeros((4,), dtype=torch.float32, device=dev)
+    p = lambda t: L.ptr(t if t.numel() else fill)
+    L.check(_lib().s2t_resample(p(waves), waves.element_size(), row_stride, L.ptr(wave_len.contiguous()), wave_len.element_size(),
+                                L.ptr(ratio_id.contiguous()) if ratio_id is not None else 0, B, Nmax, Mmax, banks.data_ptr(), banks.shape[0],
+                                p(first.contiguous()), first.shape[0], p(weights.contiguous()), weights.shape[0], p(out), L.ptr(out_len),
+                                L.ptr(status), L.stream()), "s2t_resample")
+    return out, out_len, status
+
+
 def embed_bwd(tokens, dout, dW, scale, pad):
     B, Ln = tokens.shape
     D = dW.shape[1]

@@ -534,6 +534,48 @@ int s2t_fbank(const void* waves, int wave_elem, long long row_stride, const long
  * Refusals, before anything is launched, in this order: S2T_OK at once for B <= 0; S2T_EINVAL for a NULL pointer (x, lengths,
  * out_len, status), len_elem other than 4 or 8, Tmax < 0, F < 1; then S2T_ENOTSUP for F > S2T_FBANK_MAX_BINS. */
 int s2t_cmvn(float* x, const void* lengths, int len_elem, int B, int Tmax, int F, int* out_len, int* status, void* stream);
+/* ---- Sinc resampling of waveforms (csrc/resample.hip): Kaldi's LinearResample as torchaudio.compliance.kaldi.resample_waveform
+ * restates it, for padded batches; a row picks its resampling from a small table of banks (speed perturbation: one launch).
+ * The rule.  A resampling is (orig, new), reduced by its gcd; lowpass_filter_width L = 6, rolloff 0.99 by default.  In float64 on
+ * the host: cutoff = rolloff * 0.5 * min(orig, new), ww = L / (2 cutoff), in_unit = orig, out_unit = new; for each phase
+ * i < out_unit, t = i / new, first[i] = ceil((t - ww) orig), last[i] = floor((t + ww) orig); tap j = 0 .. last[i] - first[i] has
+ * D = (first[i] + j) / orig - t and the weight w[i][j] = [|D| < ww] * 0.5 (1 + cos(2 pi cutoff / L * D)) * s(D) / orig with
+ * s(D) = sin(2 pi cutoff D) / (pi D), s(0) = 2 cutoff.  Weights are rounded to float32 once and padded with zeros to `taps`, the
+ * widest phase.  Output k of an utterance of n samples, with u = k / out_unit and i = k % out_unit, is
+ *   y[k] = the sum over j < taps of w[i][j] * x[first[i] + u * in_unit + j],   x = 0 outside [0, n)
+ * (zero, not what lies behind n in the row), summed in float32 from 0 in ascending j with fused multiply-adds.  The utterance
+ * yields m = ceil(n * out_unit / in_unit) samples (Kaldi's tick count: every output time is strictly below n / orig).  A bank with
+ * in_unit == out_unit copies: y[k] = x[k], int16 at its integer value.
+ * The table: `banks` is HOST memory, read during the call only, [n_banks][S2T_RESAMPLE_BANK_INTS] int32 =
+ * (in_unit, out_unit, taps, first_off, w_off, lo, extra): first[first_off + i] is first[i]; weights[w_off + j * out_unit + i] is
+ * w[i][j] (tap-major); lo = min first[i]; extra = max first[i] - lo + taps.  Of a copying bank only the first two are looked at.
+ * `first` (int32 [n_first]) and `weights` (float32 [n_weights]) are device memory.  A first[i] outside [lo, lo + extra - taps] is
+ * read as the nearer end: whatever the table holds, no read leaves the staged samples.
+ * Operands: waves [B] rows of Nmax elements, row_stride elements apart (int16 for wave_elem 2, float32 for 4; no alignment beyond
+ * the element's), lengths [B] int32 or int64 (len_elem 4 or 8), ratio_id [B] int32 or NULL (every row takes bank 0).
+ * out [B][Mmax] float32, out_len [B] int64, status [B] int32.  Status: 0 done; 1 no samples (n = 0); 2 refused (a length that is
+ * negative or above Nmax, a ratio_id outside [0, n_banks), m > Mmax).  out_len is 0 unless done.  Every element of out at or behind
+ * out_len[b] is written as zero, every element in front of it once: out needs no initialisation; nothing else is written.
+ * One launch, no atomics, no host read.  A workgroup takes S2T_RESAMPLE_REUSE * G units of a row, G the largest count with
+ * G * out_unit <= S2T_RESAMPLE_TILE_ITEMS and (S2T_RESAMPLE_REUSE * G - 1) * in_unit + extra <= S2T_RESAMPLE_MAX_SPAN
+ * (G = S2T_RESAMPLE_TILE_ITEMS for a copy); a result does not depend on the batch around it or on the tile it falls in.
+ * Refusals, before anything is launched, in this order: S2T_OK at once for B <= 0; S2T_EINVAL for a NULL pointer (all but ratio_id
+ * and stream are required), wave_elem other than 2 or 4, len_elem other than 4 or 8, a negative Nmax, Mmax, row_stride, n_first or
+ * n_weights, n_banks < 1; S2T_ENOTSUP for n_banks > S2T_RESAMPLE_MAX_BANKS; then bank by bank S2T_EINVAL for in_unit or
+ * out_unit < 1, taps < 1, extra < taps, a negative offset, a range of first or weights past n_first or n_weights, |lo| >= 2^30;
+ * then S2T_ENOTSUP for a bank with out_unit > S2T_RESAMPLE_MAX_PHASES, taps * out_unit > S2T_RESAMPLE_MAX_BANK or G < 1 (a
+ * span of S2T_RESAMPLE_REUSE units that does not fit: (S2T_RESAMPLE_REUSE - 1) * in_unit + extra > S2T_RESAMPLE_MAX_SPAN), and for
+ * B * tiles >= 2^31. */
+#define S2T_RESAMPLE_MAX_BANKS 8
+#define S2T_RESAMPLE_BANK_INTS 7
+#define S2T_RESAMPLE_REUSE 4
+#define S2T_RESAMPLE_TILE_ITEMS 512
+#define S2T_RESAMPLE_MAX_PHASES 512
+#define S2T_RESAMPLE_MAX_BANK 8192
+#define S2T_RESAMPLE_MAX_SPAN 7672
+int s2t_resample(const void* waves, int wave_elem, long long row_stride, const void* lengths, int len_elem, const int* ratio_id,
+                 int B, int Nmax, int Mmax, const int* banks, int n_banks, const int* first, int n_first, const float* weights,
+                 int n_weights, float* out, long long* out_len, int* status, void* stream);
 /* label_smoothed_nll_loss over log_softmax(logits.float()) (label_smoothed_cross_entropy.py:12-29), fused
  * with its gradient: sums2[0] += loss, sums2[1] += nll (caller zeroes); dlogits may be NULL. */
 int s2t_lsce(int dtype, const void* logits, const long long* target, void* dlogits, float* sums2,
