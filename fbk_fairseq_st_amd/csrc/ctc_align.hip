@@ -12,6 +12,7 @@
 // every thread owns runs of 16 states.  In both a run's back-pointers of a frame are one dword.  No atomics, no host read.
 #include "common.hpp"
 #include "ctc_rows.hpp"
+#include "prof.hpp"
 #include "s2t_hip.h"
 
 namespace {
@@ -19,21 +20,6 @@ namespace {
 constexpr int ALN_BLOCK = 64;                                       // frames per block of the backward walk (form A: 16 KiB of LDS)
 
 // ------------------------------------------------------------------ row phase
-// row_for_each with ONE assignment of columns to lanes whether or not the row starts 16-byte aligned (an unaligned row is read by
-// scalar loads in the vector sweep's order): a sum taken with it does not depend on where the row lies, so a sentence's result does
-// not depend on its place in a batch whose row stride is no multiple of 16 bytes.
-template <typename T, typename F>
-__device__ __forceinline__ void row_for_each_fixed(const T* __restrict__ x, int V, int lane, F f) {
-    constexpr int E = 16 / (int)sizeof(T);
-    const int nv = V / E;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) { row_for_each<T>(x, V, lane, f); return; }
-    for (int c = lane; c < nv; c += 64) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) f(to_f32(x[c * E + e]), c * E + e);
-    }
-    for (int j = nv * E + lane; j < V; j += 64) f(to_f32(x[j]), j);
-}
-
 // em [T*B][Lmax + 1]: column 0 the blank's log-probability, column 1 + i that of token i (-inf for a token outside [0, V): the
 // sentence phase refuses the sentence).  Rows t >= in_len[b] and sentences whose tgt_len is out of range are skipped.
 template <typename T>
@@ -415,6 +401,7 @@ extern "C" int s2t_ctc_align(int dtype, const void* logits, const int* in_len, c
         hipLaunchKernelGGL(ctc_align_row_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, in_len, targets, tgt_len, em, T, B, V, ld, Lmax, blank);
     S2T_LAUNCH_CHECK();
     const int S = 2 * Lmax + 1;
+    ProfScope prof("ctc_align_sentences", st, 0, 0);               // the sentence phase alone (tools/ctc_segment_time.py)
 #define ALN_ARGS st, em, in_len, targets, tgt_len, bp, states, frames, tok_score, score, status, T, B, V, Lmax, blank
     if (S <= 64) align_launch_wave<1>(ALN_ARGS);
     else if (S <= 128) align_launch_wave<2>(ALN_ARGS);

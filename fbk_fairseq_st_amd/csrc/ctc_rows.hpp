@@ -1,4 +1,4 @@
-// Row helpers shared by the CTC inference kernels (ctc_decode.hip, ctc_align.hip): one wave sweeps one row of logits.
+// Row helpers shared by the CTC inference kernels (ctc_decode.hip, ctc_align.hip, ctc_segment.hip): one wave sweeps one row of logits.
 #pragma once
 #include "common.hpp"
 
@@ -13,6 +13,21 @@ __device__ __forceinline__ void row_for_each(const T* __restrict__ x, int V, int
         *reinterpret_cast<u32x4*>(v) = *reinterpret_cast<const u32x4*>(x + c * E);
 #pragma unroll
         for (int e = 0; e < E; ++e) f(to_f32(v[e]), c * E + e);
+    }
+    for (int j = nv * E + lane; j < V; j += 64) f(to_f32(x[j]), j);
+}
+
+// row_for_each with ONE assignment of columns to lanes whether or not the row starts 16-byte aligned (an unaligned row is read by
+// scalar loads in the vector sweep's order): a sum taken with it does not depend on where the row lies, so a sentence's result does
+// not depend on its place in a batch whose row stride is no multiple of 16 bytes.
+template <typename T, typename F>
+__device__ __forceinline__ void row_for_each_fixed(const T* __restrict__ x, int V, int lane, F f) {
+    constexpr int E = 16 / (int)sizeof(T);
+    const int nv = V / E;
+    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) { row_for_each<T>(x, V, lane, f); return; }
+    for (int c = lane; c < nv; c += 64) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) f(to_f32(x[c * E + e]), c * E + e);
     }
     for (int j = nv * E + lane; j < V; j += 64) f(to_f32(x[j]), j);
 }

@@ -777,6 +777,71 @@ def ctc_align(logits, in_len, targets, tgt_len, blank):
     return states, frames, tok_score, score, status
 
 
+CTC_SEGMENT_MAX_TARGET = 16383    # S2T_CTC_SEGMENT_MAX_TARGET of include/s2t_hip.h
+CTC_SEGMENT_MAX_UTT = 4096        # S2T_CTC_SEGMENT_MAX_UTT
+CTC_SEGMENT_MAX_WINDOW = 4096     # S2T_CTC_SEGMENT_MAX_WINDOW
+
+
+def ctc_segment_workspace(T, B, Lmax, Umax):
+    """bytes of workspace s2t_ctc_segment takes for this shape: 4*T*B*(3 + ceil((2*Lmax + 1) / 16)) rounded up to 256"""
+    return int(_lib().s2t_ctc_segment_workspace(int(T), int(B), int(Lmax), int(Umax)))
+
+
+def ctc_segment(logits, in_len, targets, tgt_len, utt_end, n_utt, blank, free_start=True, free_end=True, window=30):
+    """CTC segmentation of recordings (include/s2t_hip.h s2t_ctc_segment states the rule): ctc_align's operands, plus the utterances
+    of every transcript as cumulative end offsets utt_end (int64 [B, Umax], the first n_utt[b] entries of a row; n_utt int64 [B]).
+    free_start / free_end: the outer blank states cost nothing; window: the frames of utt_conf_min's sliding mean.  Returns device
+    tensors (states int32 [B, T], frames int32 [B, Lmax, 2], tok_score f32 [B, Lmax], score f32 [B], utt_frames int32 [B, Umax, 2],
+    utt_score, utt_conf_mean, utt_conf_min f32 [B, Umax], status int32 [B]).  Entries behind a recording's lengths are not written,
+    nor is anything but the status of a refused recording (status 2).  T = 0 launches nothing and validates nothing: every
+    recording gets status 1 (no frames, no path) and the whole padded width of its outputs is filled with -1 / -inf, also for a
+    recording the kernel would refuse."""
+    T, B, V, in_len = _ctc_decode_args(logits, in_len, "ctc_segment")
+    if targets.dim() != 2 or targets.shape[0] != B or targets.dtype != torch.int64:
+        raise ValueError("ctc_segment: targets must be int64 [%d, Lmax], got %s %s" % (B, targets.dtype, tuple(targets.shape)))
+    if utt_end.dim() != 2 or utt_end.shape[0] != B or utt_end.dtype != torch.int64:
+        raise ValueError("ctc_segment: utt_end must be int64 [%d, Umax], got %s %s" % (B, utt_end.dtype, tuple(utt_end.shape)))
+    for name, t in (("tgt_len", tgt_len), ("n_utt", n_utt)):
+        if tuple(t.shape) != (B,) or t.dtype != torch.int64:
+            raise ValueError("ctc_segment: %s must be int64 [%d], got %s %s" % (name, B, t.dtype, tuple(t.shape)))
+    Lmax, Umax, window = targets.shape[1], utt_end.shape[1], int(window)
+    if not 1 <= Lmax <= CTC_SEGMENT_MAX_TARGET:
+        raise ValueError("ctc_segment: transcripts of 1 to %d tokens (S2T_CTC_SEGMENT_MAX_TARGET), got a padded width of %d"
+                         % (CTC_SEGMENT_MAX_TARGET, Lmax))
+    if not 1 <= Umax <= CTC_SEGMENT_MAX_UTT:
+        raise ValueError("ctc_segment: 1 to %d utterances per recording (S2T_CTC_SEGMENT_MAX_UTT), got a padded width of %d"
+                         % (CTC_SEGMENT_MAX_UTT, Umax))
+    if not 1 <= window <= CTC_SEGMENT_MAX_WINDOW:
+        raise ValueError("ctc_segment: window must lie in [1, %d] (S2T_CTC_SEGMENT_MAX_WINDOW), got %d" % (CTC_SEGMENT_MAX_WINDOW, window))
+    dev = logits.device
+    targets, tgt_len, utt_end, n_utt = targets.contiguous(), tgt_len.contiguous(), utt_end.contiguous(), n_utt.contiguous()
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frames = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    tok_score = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    utt_frames = torch.empty((B, Umax, 2), dtype=torch.int32, device=dev)
+    utt_score, utt_mean, utt_min = (torch.empty((B, Umax), dtype=torch.float32, device=dev) for _ in range(3))
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    out = (states, frames, tok_score, score, utt_frames, utt_score, utt_mean, utt_min, status)
+    if B == 0:
+        return out
+    if T == 0:                                         # no frames, no path: every transcript here has a token
+        status.fill_(1)
+        score.fill_(float("-inf"))
+        frames.fill_(-1)
+        utt_frames.fill_(-1)
+        for t in (tok_score, utt_score, utt_mean, utt_min):
+            t.fill_(float("-inf"))
+        return out
+    ws = torch.empty((ctc_segment_workspace(T, B, Lmax, Umax),), dtype=torch.uint8, device=dev)
+    flags = (1 if free_start else 0) | (2 if free_end else 0)
+    L.check(_lib().s2t_ctc_segment(L.dt(logits), L.ptr(logits), L.ptr(in_len), L.ptr(targets), L.ptr(tgt_len), L.ptr(utt_end), L.ptr(n_utt),
+                                   L.ptr(ws), L.ptr(states), L.ptr(frames), L.ptr(tok_score), L.ptr(score), L.ptr(utt_frames),
+                                   L.ptr(utt_score), L.ptr(utt_mean), L.ptr(utt_min), L.ptr(status), T, B, V, _row_ld(logits), Lmax, Umax,
+                                   int(blank), flags, window, L.stream()), "s2t_ctc_segment")
+    return out
+
+
 EDIT_MAX_A = 32767                # S2T_EDIT_MAX_A of include/s2t_hip.h
 EDIT_MAX_B = 4095                 # S2T_EDIT_MAX_B
 

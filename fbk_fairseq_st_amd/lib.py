@@ -68,6 +68,8 @@ SIGNATURES = {
     "s2t_ctc_prefix_beam": [c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "s2t_ctc_align_workspace": [c_int, c_int, c_int],               # returns size_t
     "s2t_ctc_align": [c_int, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "s2t_ctc_segment_workspace": [c_int, c_int, c_int, c_int],      # returns size_t
+    "s2t_ctc_segment": [c_int] + [P] * 16 + [c_int] * 9 + [P],
     "s2t_edit_align_workspace": [c_int, c_int, c_int, c_int],       # returns size_t
     "s2t_edit_align": [P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, P, P, P, P, P, P, P, P, P],
     "s2t_bleu_stats": [P, P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, P, P, P],
@@ -229,7 +231,7 @@ FAST_PATH = os.path.join(_HERE, "_s2t_fastcall.so")
 _HOST_SIDE = ("s2t_host_batch_by_size", "s2t_host_ctc_uer")          # CPU work: release the GIL around the call, as ctypes does
 _SIZE_T_RESULT = ("s2t_gemm_relu_mask_bytes", "s2t_attn_keep_bytes", "s2t_layer_ws_bytes", "s2t_layer_bwd_tmp_bytes", "s2t_decode_lds_bytes",
                   "s2t_ctc_loss_any_workspace", "s2t_ctc_greedy_workspace", "s2t_ctc_prefix_beam_workspace",
-                  "s2t_ctc_align_workspace", "s2t_edit_align_workspace")
+                  "s2t_ctc_align_workspace", "s2t_ctc_segment_workspace", "s2t_edit_align_workspace")
 
 
 def signature_hash():

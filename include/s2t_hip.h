@@ -394,6 +394,45 @@ size_t s2t_ctc_align_workspace(int T, int B, int Lmax);
 int s2t_ctc_align(int dtype, const void* logits, const int* in_len, const long long* targets, const long long* tgt_len, void* ws,
                   int* states, int* frames, float* tok_score, float* score, int* status, int T, int B, int V, int ld, int Lmax,
                   int blank, void* stream);
+/* ---- CTC segmentation of long recordings (csrc/ctc_segment.hip): s2t_ctc_align's rule with free ends, for transcripts given as a
+ * list of utterances, with every utterance's frames and how well it fits.  logits, in_len, targets, tgt_len, lp_v, blank as above.
+ * A recording of L = tgt_len[b] tokens is the concatenation of U = n_utt[b] utterances; utt_end int64 [B][Umax] holds their
+ * cumulative end offsets (strictly ascending, the first >= 1, the last == L), n_utt int64 [B].
+ * Rule: states, z_s, predecessors, tie rule, initialisation and end decision are s2t_ctc_align's.  flags bit 0 (free_start): state 0
+ * costs 0 on every frame instead of lp_t[blank], audio before the text is absorbed at no cost; bit 1 (free_end): the same for state
+ * S - 1.  With flags = 0 the rule IS s2t_ctc_align's, and states, frames, tok_score and score come out with the same bits.
+ * status [B] int32: 0 segmented;  1 no path (the best end value is -inf; n = 0);  2 refused: tgt_len[b] outside [1, Lmax], n_utt[b]
+ * outside [1, Umax], offsets that break the rule above, or one of the first L tokens equal to the blank or outside [0, V).  Nothing
+ * outside the row is read for a refused recording and, apart from status, none of its outputs is written.
+ * states [B][T], frames [B][Lmax][2], tok_score [B][Lmax], score [B]: as s2t_ctc_align gives them, the free frames counting 0 in
+ * score; for status 1 states -1, the first L of frames / tok_score (-1, -1) / -inf, score -inf.
+ * utt_frames [B][Umax][2] int32: the first frame of the utterance's first token, one past the last frame of its last token (blank
+ * frames between two utterances belong to neither).  utt_score [B][Umax] f32: the sum of lp_t[z_{state_t}] over that span, the blanks
+ * inside it included.  utt_conf_mean: utt_score / the span's frame count.  utt_conf_min: the lowest mean of lp_t[z_{state_t}] over
+ * `window` consecutive frames inside the span, the span's own mean when it is shorter than `window`.  Entries u >= U are not
+ * written; for status 1 the first U are (-1, -1) / -inf.
+ * A recording's result depends neither on B, nor on its place in the batch, nor on Lmax, Umax or T.  All arithmetic in f32, no atomics,
+ * no memset, no host read.  NaN logits: the path is unspecified; the call terminates and stays inside its buffers.
+ * Refusals, before anything is launched, in this order: S2T_OK at once for T*B <= 0; S2T_EINVAL for a NULL pointer, V < 2, ld < V,
+ * blank outside [0, V), Lmax < 1, Umax < 1, T*B > 2^31 - 1, flags outside [0, 3]; S2T_ENOTSUP for a dtype other than f32 / bf16,
+ * Lmax > S2T_CTC_SEGMENT_MAX_TARGET, Umax > S2T_CTC_SEGMENT_MAX_UTT, window outside [1, S2T_CTC_SEGMENT_MAX_WINDOW].
+ * Three launches: a row phase (one wave per row writes its maximum and log-sum-exp, 8 bytes), a recording phase (one workgroup of up
+ * to 1,024 threads per recording, 2 to 32 states per thread in registers, the logits of a thread's tokens gathered from the frame's
+ * row, 2-bit back-pointers, the backward walk staged through LDS in blocks of 64 frames), an utterance phase (one workgroup per
+ * utterance).
+ * ws: s2t_ctc_segment_workspace(T, B, Lmax, Umax) = 4*T*B*(3 + ceil((2*Lmax + 1) / 16)) bytes rounded up to 256 (per row its maximum
+ * and log-sum-exp, per frame the path's emission, then one dword of back-pointers per frame and 16 states); 0 for an empty problem or
+ * an Lmax or Umax out of range. */
+#define S2T_CTC_SEGMENT_MAX_TARGET 16383
+#define S2T_CTC_SEGMENT_MAX_UTT 4096
+#define S2T_CTC_SEGMENT_MAX_WINDOW 4096
+#define S2T_CTC_SEGMENT_FREE_START 1
+#define S2T_CTC_SEGMENT_FREE_END 2
+size_t s2t_ctc_segment_workspace(int T, int B, int Lmax, int Umax);
+int s2t_ctc_segment(int dtype, const void* logits, const int* in_len, const long long* targets, const long long* tgt_len,
+                    const long long* utt_end, const long long* n_utt, void* ws, int* states, int* frames, float* tok_score, float* score,
+                    int* utt_frames, float* utt_score, float* utt_conf_mean, float* utt_conf_min, int* status, int T, int B, int V, int ld,
+                    int Lmax, int Umax, int blank, int flags, int window, void* stream);
 /* ---- Edit-distance alignment of token sequences (csrc/edit_align.hip): cost, step counts and optionally the path, per sentence.
  * One sentence is a pair `a` (n tokens, the rows) and `b` (m tokens, the columns).  The three integer costs `cs`, `ca`, `cb`, each
  * in [1, 255], price a substitution, an `a` token left alone, and a `b` token left alone.
