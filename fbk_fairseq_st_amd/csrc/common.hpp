@@ -100,6 +100,14 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
     return r;
 }
 
+// A workgroup barrier that orders LDS only: global loads that were requested and global stores that were issued stay in flight
+// across it, where a __syncthreads() waits for every outstanding load of the wave.  For loops and phase chains that hand values
+// through LDS while requests fly (the device search's phases, one barrier per frame or step of the CTC and edit-distance lattices).
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
 // S2T_ACT_* of include/s2t_hip.h
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_RELU_BWD = 3, ACT_GELU_BWD = 4, ACT_RELU_MASK = 5, ACT_RELU_BWD_MASK = 6 };
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }

@@ -1,8 +1,8 @@
 // CTC forced alignment (include/s2t_hip.h: s2t_ctc_align): the most likely CTC path among those that collapse to a GIVEN
 // transcript, with the frames and the score of every token.  The split of ctc_decode.hip:
 //   * a row phase, one wave per (t, b) row with 16-byte loads: the row's maximum and its first index, the sum of exp over the other
-//     columns from the L2-resident row, then the L + 1 emissions the sentence needs -- lp[blank], lp[y_0 .. y_{L-1}] -- gathered
-//     from the row that has just been streamed.  No [rows][V] tensor exists;
+//     columns from the L2-resident row (ctc_rows.hpp: row_max_lse), then the L + 1 emissions the sentence needs -- lp[blank],
+//     lp[y_0 .. y_{L-1}] -- gathered from the row that has just been streamed.  No [rows][V] tensor exists;
 //   * a sentence phase that walks the frames keeping only the previous frame's values, writes a 2-bit back-pointer per
 //     (frame, state) to the workspace, then walks them backwards through LDS, a block of frames at a time, and derives `states`,
 //     `frames`, `tok_score` and `score` from the path in the same launch.
@@ -10,8 +10,9 @@
 // consecutive states in registers, the two values below a lane's run come by two shuffles per frame, no barrier in the loop.
 // B (Lmax <= S2T_CTC_ALIGN_MAX_TARGET): one 256-thread workgroup per sentence, two LDS rows of values, one barrier per frame,
 // every thread owns runs of 16 states.  In both a run's back-pointers of a frame are one dword.  No atomics, no host read.
+// The frame step of the recursion and the sums over the walked path are ctc_lattice.hpp's: ctc_segment.hip runs the same code.
 #include "common.hpp"
-#include "ctc_rows.hpp"
+#include "ctc_lattice.hpp"
 #include "prof.hpp"
 #include "s2t_hip.h"
 
@@ -35,45 +36,19 @@ __global__ __launch_bounds__(256) void ctc_align_row_kernel(const T* __restrict_
     if (Lq < 0 || Lq > Lmax) return;
     const int L = (int)Lq;
     const T* x = logits + row * ld;
-    float m = -INFINITY; int mi = 0x7fffffff;
-    row_for_each_fixed<T>(x, V, lane, [&](float v, int j) { if (mi == 0x7fffffff || v > m || (v == m && j < mi)) { m = v; mi = j; } });
-    wave_best(m, mi);
-    float s = 0.f;
-    row_for_each_fixed<T>(x, V, lane, [&](float v, int j) { if (j != mi) s += expf(v - m); });
-    const float lse1 = log1pf(wave_sum(s));                        // log of the row's sum of exp(x - m): 1 for column mi, R for the rest
+    const RowStat st = row_max_lse<T, true>(x, V, lane);
     float* e = em + row * (Lmax + 1);
     const long long* y = targets + (long)b * Lmax;
     for (int i = lane; i <= L; i += 64) {
         const long long c = i == 0 ? (long long)blank : y[i - 1];
-        e[i] = (c >= 0 && c < V) ? (to_f32(x[c]) - m) - lse1 : -INFINITY;
+        e[i] = (c >= 0 && c < V) ? (to_f32(x[c]) - st.m) - st.lse1 : -INFINITY;
     }
 }
 
-// ------------------------------------------------------------------ sentence phase: shared pieces
-// One frame of the recursion for a run of K consecutive states held in v (v[j] = state s0 + j), in place from the top state down
-// so that every state still sees the previous frame below it.  p1 / p2: the previous frame's values of states s0 - 1 / s0 - 2.
-// eb / et: the frame's emissions of the blank and of the run's tokens (K = 1: et[0] is the one token, `odd0` says the state is one).
-// skip / live: bit j = state s0 + j may take s0 + j - 2 / exists.  Among equal values the higher predecessor wins (strict >).
-// Returns the run's back-pointers, 2 bits per state: 0 stay, 1 advance, 2 skip.
-template <int K>
-__device__ __forceinline__ uint32_t align_step(float (&v)[K], float p1, float p2, const float* et, float eb, uint32_t skip,
-                                               uint32_t live, bool odd0) {
-    uint32_t bits = 0;
-#pragma unroll
-    for (int j = K - 1; j >= 0; --j) {
-        const float a1 = j >= 1 ? v[j >= 1 ? j - 1 : 0] : p1;
-        const float a2 = j >= 2 ? v[j >= 2 ? j - 2 : 0] : (j == 1 ? p1 : p2);
-        float best = v[j]; uint32_t k = 0;
-        if (a1 > best) { best = a1; k = 1; }
-        if (((skip >> j) & 1) && a2 > best) { best = a2; k = 2; }
-        const float e = K == 1 ? (odd0 ? et[0] : eb) : ((j & 1) ? et[j >> 1] : eb);
-        v[j] = ((live >> j) & 1) ? e + best : -INFINITY;
-        bits |= k << (2 * j);
-    }
-    return bits;
-}
+// ------------------------------------------------------------------ sentence phase: what the two forms share
+// The frame step, the outputs without a path and the emit block are ctc_lattice.hpp's, shared with ctc_segment.hip.
 
-// skip / live bits of the run of K states from s0 (S = 2 L + 1 states exist)
+// skip / live bits of the run of K states from s0 (S = 2 L + 1 states exist), as lattice_step takes them
 template <int K>
 __device__ __forceinline__ void align_run_bits(const long long* __restrict__ y, int s0, int S, uint32_t& skip, uint32_t& live) {
     skip = live = 0;
@@ -83,14 +58,6 @@ __device__ __forceinline__ void align_run_bits(const long long* __restrict__ y, 
         if (s < S) live |= 1u << j;
         if ((s & 1) && s >= 3 && s < S && y[(s - 1) >> 1] != y[(s - 3) >> 1]) skip |= 1u << j;
     }
-}
-
-// what a sentence without a path gets: states -1, and -- when its length L is usable -- (-1, -1) / -inf for its L tokens
-__device__ void align_fail(int code, int L, int* __restrict__ st, int* __restrict__ fr, float* __restrict__ ts, float* __restrict__ score,
-                           int* __restrict__ status, int Tn, int tid, int nt) {
-    for (int t = tid; t < Tn; t += nt) st[t] = -1;
-    for (int i = tid; i < L; i += nt) { fr[2 * i] = fr[2 * i + 1] = -1; ts[i] = -INFINITY; }
-    if (tid == 0) { *score = -INFINITY; *status = code; }
 }
 
 // The backward walk over cnt consecutive frames by ONE wave, from their back-pointers staged in LDS (sbp: W dwords per frame, dword
@@ -104,35 +71,9 @@ __device__ __forceinline__ void align_walk(const uint32_t* sbp, int W, int cnt, 
     }
 }
 
-// Everything the path gives for the block of frames t0 .. t0 + cnt - 1 (cnt <= 64), lane i holding the state of frame t0 + i in `mine`
-// (-1 behind cnt).  In: s = the state of frame t0 - 1, s_after = that of frame t0 + cnt (-1 at the end), carry = the sum of lp over
-// the run of s_after from t0 + cnt on.  Out: s_after / carry for the block before this one.  A token's frames are one run of equal
-// states, so its score is a segmented suffix sum and the run's first frame writes it.  Blocks are 64 frames in both forms: the sums
-// are taken in one order whatever the padded width.
-__device__ __forceinline__ void align_emit_block(const float* __restrict__ em, int t0, int cnt, int lane, int b, int B, int Lmax, int mine,
-                                                 int s, int& s_after, float& carry, float& total, int* __restrict__ st,
-                                                 int* __restrict__ fr, float* __restrict__ ts) {
-    const bool valid = lane < cnt;
-    const int t = t0 + lane;
-    if (valid) st[t] = mine;
-    int prev = __shfl_up(mine, 1), next = __shfl_down(mine, 1);
-    if (lane == 0) prev = t0 > 0 ? s : -2;
-    if (lane == cnt - 1) next = s_after;
-    const float lp = valid ? em[((long)t * B + b) * (Lmax + 1) + ((mine & 1) ? 1 + (mine >> 1) : 0)] : 0.f;
-    float sv = lp;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float ov = __shfl_down(sv, o); const int om = __shfl_down(mine, o);
-        if (lane + o < 64 && om == mine) sv += ov;
-    }
-    if (valid && mine == s_after) sv += carry;
-    if (valid && (mine & 1)) {
-        const int i = mine >> 1;
-        if (mine != prev) { fr[2 * i] = t; ts[i] = sv; }
-        if (mine != next) fr[2 * i + 1] = t + 1;
-    }
-    carry = __shfl(sv, 0); s_after = __shfl(mine, 0);
-    total += lp;
+// The emission of lane i's state `mine` at frame t0 + i of a walked block of cnt frames, from the table: lattice_emit_block's lp
+__device__ __forceinline__ float align_path_lp(const float* __restrict__ em, int t0, int cnt, int lane, int b, int B, int Lmax, int mine) {
+    return lane < cnt ? em[((long)(t0 + lane) * B + b) * (Lmax + 1) + ((mine & 1) ? 1 + (mine >> 1) : 0)] : 0.f;
 }
 
 // ------------------------------------------------------------------ form A: one sentence, one wave, K states per lane
@@ -150,13 +91,13 @@ __global__ __launch_bounds__(64) void ctc_align_wave_kernel(const float* __restr
     int* st = states + (long)b * Tn; int* fr = frames + (long)b * Lmax * 2; float* ts = tok_score + (long)b * Lmax;
     const long long* y = targets + (long)b * Lmax;
     const long long Lq = tgt_len[b];
-    if (Lq < 0 || Lq > Lmax) { align_fail(2, 0, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
+    if (Lq < 0 || Lq > Lmax) { lattice_fail(2, 0, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
     const int L = (int)Lq, S = 2 * L + 1;
     bool bad = false;
     for (int i = lane; i < L; i += 64) { const long long c = y[i]; bad = bad || c < 0 || c >= V || c == blank; }
-    if (__ballot(bad)) { align_fail(2, L, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
+    if (__ballot(bad)) { lattice_fail(2, L, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
     if (n == 0) {
-        if (L > 0) { align_fail(1, L, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
+        if (L > 0) { lattice_fail(1, L, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
         for (int t = lane; t < Tn; t += 64) st[t] = -1;
         if (lane == 0) { score[b] = 0.f; status[b] = 0; }
         return;
@@ -196,7 +137,7 @@ __global__ __launch_bounds__(64) void ctc_align_wave_kernel(const float* __restr
             const int t = tg + d;
             if (t >= n) break;
             const float eb = cb[d];
-            const float* et = ct[d];
+            const float (&et)[KT] = ct[d];
             if (t == 0) {
 #pragma unroll
                 for (int j = 0; j < K; ++j) {
@@ -209,7 +150,9 @@ __global__ __launch_bounds__(64) void ctc_align_wave_kernel(const float* __restr
             float p2 = K >= 2 ? __shfl_up(v[K >= 2 ? K - 2 : 0], 1) : __shfl_up(v[0], 2);
             if (lane == 0) p1 = p2 = -INFINITY;
             if (K == 1 && lane == 1) p2 = -INFINITY;
-            bp[((long)b * Tn + t) * 64 + lane] = align_step<K>(v, p1, p2, et, eb, skip, live, odd0);
+            uint32_t bits[1];
+            lattice_step<K>(v, p1, p2, et, eb, skip, live, 0u, bits, odd0);
+            bp[((long)b * Tn + t) * 64 + lane] = bits[0];
         }
     }
 #pragma unroll
@@ -219,7 +162,7 @@ __global__ __launch_bounds__(64) void ctc_align_wave_kernel(const float* __restr
     __syncthreads();
     const float e1 = s_v[S - 1], e2 = S >= 2 ? s_v[S - 2] : -INFINITY;
     int s = e2 > e1 ? S - 2 : S - 1;
-    if (!(fmaxf(e1, e2) > -INFINITY)) { align_fail(1, L, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
+    if (!(fmaxf(e1, e2) > -INFINITY)) { lattice_fail(1, L, st, fr, ts, score + b, status + b, Tn, lane, 64); return; }
     int s_after = -1;
     float carry = 0.f, total = 0.f;
     for (int t0 = (n - 1) / ALN_BLOCK * ALN_BLOCK; t0 >= 0; t0 -= ALN_BLOCK) {
@@ -231,18 +174,12 @@ __global__ __launch_bounds__(64) void ctc_align_wave_kernel(const float* __restr
         __syncthreads();
         int mine = -1;
         align_walk<K>(s_bp, 64, cnt, t0 == 0, lane, 0, s, mine);
-        align_emit_block(em, t0, cnt, lane, b, B, Lmax, mine, s, s_after, carry, total, st, fr, ts);
+        const float lp = align_path_lp(em, t0, cnt, lane, b, B, Lmax, mine);
+        lattice_emit_block(lp, t0, cnt, lane, mine, s, s_after, carry, total, st, fr, ts);
     }
     for (int t = n + lane; t < Tn; t += 64) st[t] = -1;
     total = wave_sum(total);
     if (lane == 0) { score[b] = total; status[b] = 0; }
-}
-
-// a workgroup barrier that orders LDS only (decode.hip's lds_barrier): the requested emissions and the back-pointer stores stay in
-// flight across it, where __syncthreads() would wait for every one of them on every frame
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
 }
 
 // Where state s lives in an LDS row of form B: inside its run of 16, rotated by (run / 4).  A thread reads its run one state at a
@@ -265,7 +202,7 @@ __global__ __launch_bounds__(256) void ctc_align_block_kernel(const float* __res
     int* st = states + (long)b * Tn; int* fr = frames + (long)b * Lmax * 2; float* ts = tok_score + (long)b * Lmax;
     const long long* y = targets + (long)b * Lmax;
     const long long Lq = tgt_len[b];
-    if (Lq < 0 || Lq > Lmax) { align_fail(2, 0, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
+    if (Lq < 0 || Lq > Lmax) { lattice_fail(2, 0, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
     const int L = (int)Lq, S = 2 * L + 1;
     int* flag = reinterpret_cast<int*>(dyn);
     if (tid == 0) *flag = 0;
@@ -276,9 +213,9 @@ __global__ __launch_bounds__(256) void ctc_align_block_kernel(const float* __res
     __syncthreads();
     const bool refused = *flag != 0;
     __syncthreads();
-    if (refused) { align_fail(2, L, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
+    if (refused) { lattice_fail(2, L, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
     if (n == 0) {
-        if (L > 0) { align_fail(1, L, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
+        if (L > 0) { lattice_fail(1, L, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
         for (int t = tid; t < Tn; t += 256) st[t] = -1;
         if (tid == 0) { score[b] = 0.f; status[b] = 0; }
         return;
@@ -329,18 +266,21 @@ __global__ __launch_bounds__(256) void ctc_align_block_kernel(const float* __res
 #pragma unroll
                     for (int q = 0; q < K; ++q) v[q] = cur[s0 + ((q + (c >> 2)) & 15)];
                     const float p1 = c > 0 ? cur[lds_slot(s0 - 1)] : -INFINITY, p2 = c > 0 ? cur[lds_slot(s0 - 2)] : -INFINITY;
-                    bp[((long)b * Tn + t) * W + c] = align_step<K>(v, p1, p2, ct[d][j], eb, skip[j], live[j], false);
+                    uint32_t bits[1];
+                    lattice_step<K>(v, p1, p2, ct[d][j], eb, skip[j], live[j], 0u, bits);
+                    bp[((long)b * Tn + t) * W + c] = bits[0];
                 }
 #pragma unroll
                 for (int q = 0; q < K; ++q) nxt[s0 + ((q + (c >> 2)) & 15)] = v[q];
             }
-            lds_barrier();
+            lds_barrier();                                          // LDS only: the requested emissions and the back-pointer stores
+                                                                    // stay in flight, a __syncthreads() would wait for them every frame
             float* sw = cur; cur = nxt; nxt = sw;
         }
     }
     const float e1 = cur[lds_slot(S - 1)], e2 = S >= 2 ? cur[lds_slot(S - 2)] : -INFINITY;
     int s = e2 > e1 ? S - 2 : S - 1;
-    if (!(fmaxf(e1, e2) > -INFINITY)) { align_fail(1, L, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
+    if (!(fmaxf(e1, e2) > -INFINITY)) { lattice_fail(1, L, st, fr, ts, score + b, status + b, Tn, tid, 256); return; }
     __threadfence();                                                // the back-pointers were written by other threads of this workgroup
     uint32_t* sbp = reinterpret_cast<uint32_t*>(dyn);               // FB frames x W dwords = the two rows
     int s_after = -1;
@@ -357,7 +297,10 @@ __global__ __launch_bounds__(256) void ctc_align_block_kernel(const float* __res
             __syncthreads();
             if (tid < 64) align_walk<K>(sbp, W, hc, t0 + h == 0, tid, h, s, mine);
         }
-        if (tid < 64) align_emit_block(em, t0, cnt, tid, b, B, Lmax, mine, s, s_after, carry, total, st, fr, ts);
+        if (tid < 64) {
+            const float lp = align_path_lp(em, t0, cnt, tid, b, B, Lmax, mine);
+            lattice_emit_block(lp, t0, cnt, tid, mine, s, s_after, carry, total, st, fr, ts);
+        }
     }
     for (int t = n + tid; t < Tn; t += 256) st[t] = -1;
     if (tid < 64) {

@@ -5,7 +5,8 @@
 //
 // Both follow the device search's split:
 //   * a row phase, one wave per (t, b) row with 16-byte loads: the row's maximum and its first index, the sum of exp over the
-//     OTHER columns (so that log-probabilities near 0 keep their relative precision: lp = (x - m) - log1p(R)), the blank's lp and
+//     OTHER columns (so that log-probabilities near 0 keep their relative precision: lp = (x - m) - log1p(R); ctc_rows.hpp's
+//     row_max_lse, the statistic ctc_align.hip and ctc_segment.hip take too), the blank's lp and
 //     -- for the beam search -- the `cand` non-blank columns of highest logit, one more sweep of the L2-resident row for each;
 //   * a sentence phase, one wave per sentence, that walks the frames.  No atomics, no host read between the two launches.
 // A prefix of the beam search is identified by its token STRING (a 64-bit hash of the string plus its length), never by the entry
@@ -36,15 +37,10 @@ __global__ __launch_bounds__(256) void ctc_decode_row_kernel(const T* __restrict
     const int t = (int)(row / B), b = (int)(row - (long)t * B);
     if (t >= in_len[b]) return;
     const T* x = logits + row * ld;
-    float m = -INFINITY; int mi = 0x7fffffff;
-    row_for_each<T>(x, V, lane, [&](float v, int j) { if (mi == 0x7fffffff || v > m || (v == m && j < mi)) { m = v; mi = j; } });
-    wave_best(m, mi);
-    float s = 0.f;
-    row_for_each<T>(x, V, lane, [&](float v, int j) { if (j != mi) s += expf(v - m); });
-    const float lse1 = log1pf(wave_sum(s));                        // log of the row's sum of exp(x - m): 1 for column mi, R for the rest
+    const RowStat st = row_max_lse<T, false>(x, V, lane);
     if (lane == 0) {
-        if (arg) { arg[row] = mi; arg_lp[row] = -lse1; }
-        if (lpb) lpb[row] = (to_f32(x[blank]) - m) - lse1;
+        if (arg) { arg[row] = st.mi; arg_lp[row] = -st.lse1; }
+        if (lpb) lpb[row] = (to_f32(x[blank]) - st.m) - st.lse1;
     }
     float pv = INFINITY; int pi = -1;                              // the previous pick: the next one comes strictly after it
     for (int r = 0; r < cand; ++r) {
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(256) void ctc_decode_row_kernel(const T* __restrict
         });
         wave_best(bv, bi);
         const bool none = bi == 0x7fffffff;                        // fewer than cand comparable columns (NaN logits): no candidate
-        if (lane == 0) { cidx[row * cand + r] = none ? -1 : bi; clp[row * cand + r] = none ? -INFINITY : (bv - m) - lse1; }
+        if (lane == 0) { cidx[row * cand + r] = none ? -1 : bi; clp[row * cand + r] = none ? -INFINITY : (bv - st.m) - st.lse1; }
         pv = none ? -INFINITY : bv; pi = bi;                      // after `none` every later round finds none too: all cand slots are written
     }
 }

@@ -40,3 +40,18 @@ __device__ __forceinline__ void wave_best(float& v, int& i) {
         if (oi != 0x7fffffff && (i == 0x7fffffff || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
     }
 }
+
+// The row statistic of all three row phases: the maximum m, its first column mi, and lse1 = log1p of the sum of exp(x - m) over the
+// OTHER columns, i.e. the log of the row's sum of exp(x - m) with column mi counted as exactly 1, so that lp = (x - m) - lse1 keeps
+// its relative precision near 0.  FIXED: sweep with row_for_each_fixed (alignment, segmentation) instead of row_for_each (decoding).
+struct RowStat { float m; int mi; float lse1; };
+template <typename T, bool FIXED>
+__device__ __forceinline__ RowStat row_max_lse(const T* __restrict__ x, int V, int lane) {
+    auto sweep = [&](auto f) { if constexpr (FIXED) row_for_each_fixed<T>(x, V, lane, f); else row_for_each<T>(x, V, lane, f); };
+    float m = -INFINITY; int mi = 0x7fffffff;
+    sweep([&](float v, int j) { if (mi == 0x7fffffff || v > m || (v == m && j < mi)) { m = v; mi = j; } });
+    wave_best(m, mi);
+    float s = 0.f;
+    sweep([&](float v, int j) { if (j != mi) s += expf(v - m); });
+    return {m, mi, log1pf(wave_sum(s))};
+}

@@ -5,15 +5,17 @@
 //   * a recording phase, one workgroup of up to 1,024 threads per recording.  Every thread owns K = 2, 4, 8, 16 or 32 consecutive
 //     states in registers and GATHERS the logits of its own K / 2 tokens from the frame's row (every thread of the workgroup reads
 //     that row in the same frame: it comes from L2), some frames ahead; the two values below a run come from the thread below through
-//     LDS behind one LDS-only barrier per frame.  Back-pointers: 2 bits per state, one dword per 16 states, as in ctc_align.hip.  The
-//     backward walk moves at most two states per frame, so of a block of 64 frames it stages only the 9 dwords per frame the path
-//     can touch; `states`, `frames`, `tok_score`, `score` and the per-frame emission of the path (frame_lp, workspace) come from the
-//     walked blocks with the sums of ctc_align.hip, in its order: with both ends pinned the two give the same bits;
+//     LDS behind one LDS-only barrier per frame.  The frame step and its back-pointers (2 bits per state, one dword per 16 states)
+//     are ctc_lattice.hpp's, the code ctc_align.hip runs.  The backward walk moves at most two states per frame, so of a block of
+//     64 frames it stages only the 9 dwords per frame the path can touch; `states`, `frames`, `tok_score`, `score` and the
+//     per-frame emission of the path (frame_lp, workspace) come from the walked blocks through ctc_lattice.hpp's emit block, the
+//     aligner's too: with both ends pinned the two give the same bits (the skip / live masks are each file's own: a test pairs
+//     every form of the two kernels);
 //   * an utterance phase, one 256-thread workgroup per (utterance, recording): the span from `frames`, its sum, mean and the lowest
 //     mean of `window` consecutive frames, from frame_lp.
 // No atomics, no memset, no host read; a workgroup never waits for another one.
 #include "common.hpp"
-#include "ctc_rows.hpp"
+#include "ctc_lattice.hpp"
 #include "prof.hpp"
 #include "s2t_hip.h"
 
@@ -39,22 +41,11 @@ __global__ __launch_bounds__(256) void ctc_segment_row_kernel(const T* __restric
     const long long Lq = tgt_len[b], Uq = n_utt[b];
     if (Lq < 1 || Lq > Lmax || Uq < 1 || Uq > Umax) return;
     const T* x = logits + row * ld;
-    float m = -INFINITY; int mi = 0x7fffffff;
-    row_for_each_fixed<T>(x, V, lane, [&](float v, int j) { if (mi == 0x7fffffff || v > m || (v == m && j < mi)) { m = v; mi = j; } });
-    wave_best(m, mi);
-    float s = 0.f;
-    row_for_each_fixed<T>(x, V, lane, [&](float v, int j) { if (j != mi) s += expf(v - m); });
-    const float lse1 = log1pf(wave_sum(s));
-    if (lane == 0) rs[row] = make_float2(m, lse1);
+    const RowStat st = row_max_lse<T, true>(x, V, lane);
+    if (lane == 0) rs[row] = make_float2(st.m, st.lse1);
 }
 
 // ------------------------------------------------------------------ recording phase
-// a workgroup barrier that orders LDS only (ctc_align.hip's lds_barrier): the requested logits and the back-pointer stores stay in flight
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
 // A logit of a row by buffer addressing: the row's descriptor is wave-uniform, a column is one 32-bit register of byte offset (a flat
 // load would keep a 64-bit address per token in registers, 32 of them at K = 32); a column past the row would load 0, none is.
 template <typename T> __device__ __forceinline__ float row_logit(__amdgpu_buffer_rsrc_t r, uint32_t off);
@@ -65,76 +56,24 @@ template <> __device__ __forceinline__ float row_logit<bf16>(__amdgpu_buffer_rsr
     return __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0) << 16);
 }
 
-// One frame of the recursion for a run of K consecutive states from an EVEN state (v[j] = state s0 + j, odd j = token j / 2 of the
-// run), in place from the top state down.  p1 / p2: the previous frame's values of s0 - 1 / s0 - 2.  eb / et: the frame's emissions
-// of the blank and of the run's tokens; zero: bit j = the state is a free outer blank, its emission is 0.  skip / live as in
-// ctc_align.hip.  Among equal values the higher predecessor wins (strict >).  bits: 2 per state, 0 stay, 1 advance, 2 skip.
-template <int K>
-__device__ __forceinline__ void seg_step(float (&v)[K], float p1, float p2, const float (&et)[K / 2], float eb, uint32_t skip, uint32_t live,
-                                         uint32_t zero, uint32_t (&bits)[(K + 15) / 16]) {
-#pragma unroll
-    for (int w = 0; w < (K + 15) / 16; ++w) bits[w] = 0;
-#pragma unroll
-    for (int j = K - 1; j >= 0; --j) {
-        const float a1 = j >= 1 ? v[j >= 1 ? j - 1 : 0] : p1;
-        const float a2 = j >= 2 ? v[j >= 2 ? j - 2 : 0] : (j == 1 ? p1 : p2);
-        float best = v[j]; uint32_t k = 0;
-        if (a1 > best) { best = a1; k = 1; }
-        if (((skip >> j) & 1) && a2 > best) { best = a2; k = 2; }
-        float e = (j & 1) ? et[j >> 1] : eb;
-        if ((zero >> j) & 1) e = 0.f;
-        v[j] = ((live >> j) & 1) ? e + best : -INFINITY;
-        bits[j >> 4] |= k << (2 * (j & 15));
-    }
-}
-
-// what a recording without a path gets (status 1): states -1, (-1, -1) / -inf for its L tokens, score -inf
-__device__ void seg_fail(int L, int* __restrict__ st, int* __restrict__ fr, float* __restrict__ ts, float* __restrict__ score,
-                         int* __restrict__ status, int Tn, int tid, int nt) {
-    for (int t = tid; t < Tn; t += nt) st[t] = -1;
-    for (int i = tid; i < L; i += nt) { fr[2 * i] = fr[2 * i + 1] = -1; ts[i] = -INFINITY; }
-    if (tid == 0) { *score = -INFINITY; *status = 1; }
-}
-
-// ctc_align.hip's align_emit_block with the path's emission gathered from the logits row instead of read from a table, and kept in
-// flp.  Lane i holds the state of frame t0 + i in `mine` (-1 behind cnt).  In: s = the state of frame t0 - 1, s_after = that of frame
-// t0 + cnt (-1 at the end), carry = the sum of lp over the run of s_after from t0 + cnt on.  Out: s_after / carry for the block before.
+// The emission of lane i's state `mine` (-1 behind cnt) at frame t0 + i of a walked block of cnt frames, gathered from the logits row
+// where ctc_align.hip reads its table (a free outer blank: 0) and kept in flp for the utterance phase: lattice_emit_block's lp.
 template <typename T>
-__device__ __forceinline__ void seg_emit_block(const T* __restrict__ logits, const float2* __restrict__ rs, const long long* __restrict__ y,
-                                               int blank, int flags, int S, int ld, int t0, int cnt, int lane, int b, int B, int mine, int s,
-                                               int& s_after, float& carry, float& total, int* __restrict__ st, int* __restrict__ fr,
-                                               float* __restrict__ ts, float* __restrict__ flp) {
-    const bool valid = lane < cnt;
+__device__ __forceinline__ float seg_path_lp(const T* __restrict__ logits, const float2* __restrict__ rs, const long long* __restrict__ y,
+                                             int blank, int flags, int S, int ld, int t0, int cnt, int lane, int b, int B, int mine,
+                                             float* __restrict__ flp) {
+    if (lane >= cnt) return 0.f;
     const int t = t0 + lane;
-    if (valid) st[t] = mine;
-    int prev = __shfl_up(mine, 1), next = __shfl_down(mine, 1);
-    if (lane == 0) prev = t0 > 0 ? s : -2;
-    if (lane == cnt - 1) next = s_after;
     float lp = 0.f;
-    if (valid) {
-        const bool free = (mine == 0 && (flags & SEG_FREE_START)) || (mine == S - 1 && (flags & SEG_FREE_END));
-        if (!free) {
-            const long row = (long)t * B + b;
-            const long long c = (mine & 1) ? y[mine >> 1] : (long long)blank;
-            const float2 r = rs[row];
-            lp = (to_f32(logits[row * ld + c]) - r.x) - r.y;
-        }
-        flp[t] = lp;
+    const bool free = (mine == 0 && (flags & SEG_FREE_START)) || (mine == S - 1 && (flags & SEG_FREE_END));
+    if (!free) {
+        const long row = (long)t * B + b;
+        const long long c = (mine & 1) ? y[mine >> 1] : (long long)blank;
+        const float2 r = rs[row];
+        lp = (to_f32(logits[row * ld + c]) - r.x) - r.y;
     }
-    float sv = lp;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float ov = __shfl_down(sv, o); const int om = __shfl_down(mine, o);
-        if (lane + o < 64 && om == mine) sv += ov;
-    }
-    if (valid && mine == s_after) sv += carry;
-    if (valid && (mine & 1)) {
-        const int i = mine >> 1;
-        if (mine != prev) { fr[2 * i] = t; ts[i] = sv; }
-        if (mine != next) fr[2 * i + 1] = t + 1;
-    }
-    carry = __shfl(sv, 0); s_after = __shfl(mine, 0);
-    total += lp;
+    flp[t] = lp;
+    return lp;
 }
 
 // Thread tid owns the states tid K .. tid K + K - 1.  bp [B][T][W] dwords, dword d of a frame holding the states 16 d .. 16 d + 15.
@@ -178,15 +117,15 @@ __global__ __launch_bounds__(1024) void ctc_segment_rec_kernel(const T* __restri
     if (s_flag != 0) { if (tid == 0) status[b] = 2; return; }
     int* st = states + (long)b * Tn; int* fr = frames + (long)b * Lmax * 2; float* ts = tok_score + (long)b * Lmax;
     float* flp = frame_lp + (long)b * Tn;
-    if (n == 0) { seg_fail(L, st, fr, ts, score + b, status + b, Tn, tid, nt); return; }
+    if (n == 0) { lattice_fail(1, L, st, fr, ts, score + b, status + b, Tn, tid, nt); return; }
 
     const int s0 = tid * K;
     uint32_t skip = 0, live = 0, zero = 0;
     uint32_t col[KT];                                               // byte offsets of the run's tokens in a row (a dead token: 0);
                                                                     // 32 bits each: a uniform row address plus one register
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const int s = s0 + j;
+    for (int j = 0; j < K; ++j) {                                   // ctc_align.hip's align_run_bits and the free outer blanks in one
+        const int s = s0 + j;                                       // loop: apart they make the frame loop slower (ctc_lattice.hpp)
         if (s < S) live |= 1u << j;
         if ((s & 1) && s >= 3 && s < S && y[(s - 1) >> 1] != y[(s - 3) >> 1]) skip |= 1u << j;
         if ((s == 0 && (flags & SEG_FREE_START)) || (s == S - 1 && (flags & SEG_FREE_END))) zero |= 1u << j;
@@ -238,7 +177,7 @@ __global__ __launch_bounds__(1024) void ctc_segment_rec_kernel(const T* __restri
                     float p1 = -INFINITY, p2 = -INFINITY;
                     if (tid > 0) { const float2 h = s_hand[(t - 1) & 1][tid - 1]; p1 = h.x; p2 = h.y; }
                     uint32_t bits[NW];
-                    seg_step<K>(v, p1, p2, et, eb, skip, live, zero, bits);
+                    lattice_step<K>(v, p1, p2, et, eb, skip, live, zero, bits);
                     uint32_t* row = bp + ((long)b * Tn + t) * W;
                     if constexpr (K >= 16) {
 #pragma unroll
@@ -251,8 +190,8 @@ __global__ __launch_bounds__(1024) void ctc_segment_rec_kernel(const T* __restri
                     }
                 }
                 s_hand[t & 1][tid] = make_float2(v[K - 1], v[K - 2]);
-                lds_barrier();
-            }
+                lds_barrier();                                      // LDS only: the requested logits and the back-pointer stores
+            }                                                       // stay in flight across it
         }
     }
 #pragma unroll
@@ -264,7 +203,7 @@ __global__ __launch_bounds__(1024) void ctc_segment_rec_kernel(const T* __restri
     __syncthreads();
     const float e1 = s_end[0], e2 = s_end[1];
     int s = e2 > e1 ? S - 2 : S - 1;
-    if (!(fmaxf(e1, e2) > -INFINITY)) { seg_fail(L, st, fr, ts, score + b, status + b, Tn, tid, nt); return; }
+    if (!(fmaxf(e1, e2) > -INFINITY)) { lattice_fail(1, L, st, fr, ts, score + b, status + b, Tn, tid, nt); return; }
     int s_after = -1;
     float carry = 0.f, total = 0.f;
     for (int t0 = (n - 1) / SEG_BLOCK * SEG_BLOCK; t0 >= 0; t0 -= SEG_BLOCK) {
@@ -281,7 +220,8 @@ __global__ __launch_bounds__(1024) void ctc_segment_rec_kernel(const T* __restri
                 if (tid == i) mine = s;
                 if (i > 0 || t0 > 0) s -= (s_bp[i * SEG_WIN + (s >> 4) - lo] >> (2 * (s & 15))) & 3;
             }
-            seg_emit_block<T>(logits, rs, y, blank, flags, S, ld, t0, cnt, tid, b, B, mine, s, s_after, carry, total, st, fr, ts, flp);
+            const float lp = seg_path_lp<T>(logits, rs, y, blank, flags, S, ld, t0, cnt, tid, b, B, mine, flp);
+            lattice_emit_block(lp, t0, cnt, tid, mine, s, s_after, carry, total, st, fr, ts);
             if (tid == 0) s_state = s;
         }
         __syncthreads();

@@ -151,12 +151,8 @@ __host__ __device__ inline FfnLds ffn_lds(int R, int D, int hs, int es) {
 // Every launch of a step is a chain of dependent phases on one wave per SIMD, so its length is (bytes streamed) / (what one CU keeps in
 // flight) + (number of DEPENDENT memory round trips) x (1-2 us each for lines another CU wrote).  The rules the kernels below follow:
 // everything whose address is known at the top of the launch is requested there, in the order in which it is needed (loads return in
-// order); workgroup barriers between the phases order LDS only (lds_barrier), so that requests stay in flight across them -- a
-// __syncthreads() waits for every outstanding load of the wave.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
+// order); workgroup barriers between the phases order LDS only (common.hpp: lds_barrier), so that requests stay in flight across
+// them -- a __syncthreads() waits for every outstanding load of the wave.
 // rows n0 .. n0+R-1:  v = x_in + bias + sum_p part_in[p]   (fixed order: the result does not depend on scheduling)
 // the writer workgroup stores v (the residual stream after the previous block) to x_out; every workgroup normalises its copy:
 // dst[r * ld + d] = T(LayerNorm(v)[d])  (fairseq/modules/layer_norm.py: eps inside the square root, biased variance, f32 statistics).

@@ -43,11 +43,6 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long x,
     const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)x, l), hi = __builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), l);
     return ((unsigned long long)hi << 32) | lo;
 }
-// a workgroup barrier that orders LDS only (ctc_align.hip's): the step stores stay in flight across it
-__device__ __forceinline__ void edit_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
 
 constexpr unsigned long long ONE_M = 1ull, ONE_S = 1ull << 16, ONE_B = 1ull << 32, ONE_A = 1ull << 48;
 
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(64 * NW) void edit_align_kernel(const EditArgs p) {
                     x[1] = (uint32_t)o_cnt; x[2] = (uint32_t)(o_cnt >> 32);
                     x[3] = (uint32_t)o_tok; x[4] = (uint32_t)(o_tok >> 32);
                 }
-                edit_lds_barrier();
+                lds_barrier();                                      // LDS only: the step stores stay in flight across it
             }
         }
         __threadfence();                                            // the steps were stored by other threads of this workgroup

@@ -16,6 +16,7 @@ Like CTCDecoder, the class is handed to `task.inference_step(aligner, models, sa
 import torch
 
 from . import kernels as K
+from .ctc_head import blank_index, encoder_logits, single_model
 
 MAX_TARGET = K.CTC_ALIGN_MAX_TARGET     # S2T_CTC_ALIGN_MAX_TARGET
 SUBSAMPLING = 4                         # two stride-2 convolutions in front of the encoder
@@ -27,35 +28,14 @@ class CTCAligner:
     """src_dict: the transcript dictionary; the blank is its `<ctc_blank>` entry."""
 
     def __init__(self, src_dict):
-        self.blank = src_dict.index("<ctc_blank>")
-        if self.blank == src_dict.unk():
-            raise ValueError("the dictionary has no <ctc_blank> entry")
+        self.blank = blank_index(src_dict)
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs):
         """per sentence a one-element list holding the dict of align_logits, for sample["transcript_target"]"""
-        models = list(models) if isinstance(models, (list, tuple)) else [models]
-        if len(models) != 1:
-            raise ValueError("CTCAligner aligns to the CTC head of exactly one model, got %d" % len(models))
-        model = models[0]
-        was_training = model.training
-        model.eval()
-        try:
-            net_input = sample["net_input"]
-            enc = model.encoder(**{k: v for k, v in net_input.items() if k in ("src_tokens", "src_lengths")})
-            logits = getattr(enc, "ctc_out", None)
-            if logits is None:
-                raise ValueError("the encoder returned no ctc_out (a model built without --ctc-compress-out): apply the criterion's "
-                                 "fc_out to its encoder state and call align_logits(logits, in_len, targets, tgt_len)")
-            mask = enc.ctc_padding_mask
-            T, B = logits.shape[0], logits.shape[1]
-            if mask is None:
-                in_len = torch.full((B,), T, dtype=torch.int32, device=logits.device)
-            else:
-                in_len = (~mask).sum(1).to(torch.int32)
-            return self.align_logits(logits, in_len, sample["transcript_target"], sample["transcript_target_lengths"])
-        finally:
-            model.train(was_training)
+        model = single_model(models, "CTCAligner aligns to the CTC head of exactly one model, got %d")
+        logits, in_len = encoder_logits(model, sample["net_input"], "align_logits(logits, in_len, targets, tgt_len)")
+        return self.align_logits(logits, in_len, sample["transcript_target"], sample["transcript_target_lengths"])
 
     @torch.no_grad()
     def align_logits(self, logits, in_len, targets, tgt_len):

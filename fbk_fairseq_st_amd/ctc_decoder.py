@@ -19,6 +19,7 @@ them; the one device-to-host copy of a call fetches the hypotheses' lengths at t
 import torch
 
 from . import kernels as K
+from .ctc_head import blank_index, encoder_logits, single_model
 
 STRATEGIES = ("greedy", "prefix")
 MAX_BEAM = MAX_CAND = 16          # s2t_ctc_prefix_beam
@@ -35,9 +36,7 @@ class CTCDecoder:
         if strategy == "prefix" and not (1 <= nbest <= beam_size <= MAX_BEAM and 1 <= cand <= MAX_CAND):
             raise ValueError("prefix search takes 1 <= nbest <= beam_size <= %d and 1 <= cand <= %d, got nbest %d, beam_size %d, cand %d"
                              % (MAX_BEAM, MAX_CAND, nbest, beam_size, cand))
-        self.blank = src_dict.index("<ctc_blank>")
-        if self.blank == src_dict.unk():
-            raise ValueError("the dictionary has no <ctc_blank> entry")
+        self.blank = blank_index(src_dict)
         self.strategy, self.beam_size, self.cand, self.nbest = strategy, int(beam_size), int(cand), int(nbest)
 
     @torch.no_grad()
@@ -46,28 +45,8 @@ class CTCDecoder:
         best path's log-probability / the prefix' log-probability over all alignments), `positional_scores` and `frames` (greedy:
         f32 [n] and int32 [n, 2] = first frame, one past the last frame, in CTC frame units; prefix: None), `attention`, `alignment`
         (None)."""
-        models = list(models) if isinstance(models, (list, tuple)) else [models]
-        if len(models) != 1:
-            raise ValueError("CTCDecoder decodes the CTC head of exactly one model, got %d" % len(models))
-        model = models[0]
-        was_training = model.training
-        model.eval()
-        try:
-            net_input = sample["net_input"]
-            enc = model.encoder(**{k: v for k, v in net_input.items() if k in ("src_tokens", "src_lengths")})
-            logits = getattr(enc, "ctc_out", None)
-            if logits is None:
-                raise ValueError("the encoder returned no ctc_out (a model built without --ctc-compress-out): apply the criterion's "
-                                 "fc_out to its encoder state and call decode_logits(logits, in_len)")
-            mask = enc.ctc_padding_mask
-            T, B = logits.shape[0], logits.shape[1]
-            if mask is None:
-                in_len = torch.full((B,), T, dtype=torch.int32, device=logits.device)
-            else:
-                in_len = (~mask).sum(1).to(torch.int32)
-            return self.decode_logits(logits, in_len)
-        finally:
-            model.train(was_training)
+        model = single_model(models, "CTCDecoder decodes the CTC head of exactly one model, got %d")
+        return self.decode_logits(*encoder_logits(model, sample["net_input"], "decode_logits(logits, in_len)"))
 
     @torch.no_grad()
     def decode_logits(self, logits, in_len):

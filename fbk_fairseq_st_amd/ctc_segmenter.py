@@ -18,6 +18,7 @@ import torch
 
 from . import kernels as K
 from .ctc_aligner import SUBSAMPLING, input_frames
+from .ctc_head import blank_index, ctc_out, eval_mode, single_model
 
 MAX_TARGET = K.CTC_SEGMENT_MAX_TARGET   # S2T_CTC_SEGMENT_MAX_TARGET
 MAX_UTT = K.CTC_SEGMENT_MAX_UTT         # S2T_CTC_SEGMENT_MAX_UTT
@@ -39,9 +40,7 @@ class CTCSegmenter:
     `conf_min`.  free_start / free_end: the path may begin / end anywhere in the recording at no cost."""
 
     def __init__(self, src_dict, window=30, free_start=True, free_end=True):
-        self.blank = src_dict.index("<ctc_blank>")
-        if self.blank == src_dict.unk():
-            raise ValueError("the dictionary has no <ctc_blank> entry")
+        self.blank = blank_index(src_dict)
         self.window = int(window)
         if not 1 <= self.window <= MAX_WINDOW:
             raise ValueError("CTCSegmenter: window must lie in [1, %d] (S2T_CTC_SEGMENT_MAX_WINDOW), got %d" % (MAX_WINDOW, self.window))
@@ -51,11 +50,9 @@ class CTCSegmenter:
     def generate(self, models, sample, **kwargs):
         """sample["net_input"]: one long recording per row (src_tokens [B, frames, features], src_lengths [B]); sample["utterances"]:
         per recording its list of token tensors.  logits_of_recording for every row, then segment_logits."""
-        models = list(models) if isinstance(models, (list, tuple)) else [models]
-        if len(models) != 1:
-            raise ValueError("CTCSegmenter segments with the CTC head of exactly one model, got %d" % len(models))
+        model = single_model(models, "CTCSegmenter segments with the CTC head of exactly one model, got %d")
         src, lengths = sample["net_input"]["src_tokens"], sample["net_input"]["src_lengths"].tolist()
-        parts = [self.logits_of_recording(models[0], src[b], lengths[b]) for b in range(src.shape[0])]
+        parts = [self.logits_of_recording(model, src[b], lengths[b]) for b in range(src.shape[0])]
         T = max([n for _, n in parts] + [1])
         logits = parts[0][0].new_zeros((T, len(parts), parts[0][0].shape[2]))
         for b, (x, n) in enumerate(parts):
@@ -86,10 +83,8 @@ class CTCSegmenter:
         (logits [n4, 1, V], n4)."""
         length = int(length)
         plan = self.window_plan(length, window_frames, context_frames)
-        was_training = model.training
-        model.eval()
-        try:
-            pieces = []
+        pieces = []
+        with eval_mode(model):
             for c in range(0, len(plan), windows_per_call):
                 chunk = plan[c:c + windows_per_call]
                 width = max(stop - start for start, stop, _, _ in chunk)
@@ -97,18 +92,12 @@ class CTCSegmenter:
                 for i, (start, stop, _, _) in enumerate(chunk):
                     src[i, :stop - start] = features[start:stop]
                 lens = torch.tensor([stop - start for start, stop, _, _ in chunk], dtype=torch.long, device=features.device)
-                enc = model.encoder(src_tokens=src, src_lengths=lens)
-                logits = getattr(enc, "ctc_out", None)
-                if logits is None:
-                    raise ValueError("the encoder returned no ctc_out (a model built without --ctc-compress-out): apply the criterion's "
-                                     "fc_out to its encoder state and call segment_logits(logits, in_len, utterances)")
+                logits, _ = ctc_out(model, {"src_tokens": src, "src_lengths": lens}, "segment_logits(logits, in_len, utterances)")
                 for i, (start, stop, lo, hi) in enumerate(chunk):
                     own = -(-(stop - start) // SUBSAMPLING)            # the CTC frames of the window's own input frames
                     pieces.append(logits[lo:own if hi is None else hi, i])
-            out = torch.cat(pieces)[:, None]
-            return out, out.shape[0]
-        finally:
-            model.train(was_training)
+        out = torch.cat(pieces)[:, None]
+        return out, out.shape[0]
 
     @staticmethod
     def chunk_recordings(T, lengths):
