@@ -28,6 +28,12 @@ def default_cfg(**kw):
     return cfg
 
 
+def _wide(x):
+    """the reference's `.float()` (softmax, log_softmax and gelu run in fp32 on a half-precision tensor), for any input: a float64
+    tensor -- checker-only, the float64 run that measures this oracle's own rounding -- stays float64"""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def site_act(cfg, site, act):
     """The activation of one site, or -- checker-only -- that site's ReLU with the ACTIVE SET taken from the caller
     (cfg["relu_masks"][site], a bool tensor in this function's layout): y = x * mask, gradient routed by the same mask.
@@ -79,19 +85,20 @@ def act_fn(name):
     if name == "relu":
         return F.relu
     if name == "gelu":
-        return lambda x: F.gelu(x.float()).type_as(x)
+        return lambda x: F.gelu(_wide(x)).type_as(x)
     raise ValueError(name)
 
 
 # ------------------------------------------------------------------ positions
-def sinusoid_table(n, dim, padding_idx):
-    """fairseq/modules/sinusoidal_positional_embedding.py:36-58: [sin | cos], row pad = 0."""
+def sinusoid_table(n, dim, padding_idx, dtype=torch.float):
+    """fairseq/modules/sinusoidal_positional_embedding.py:36-58: [sin | cos], row pad = 0.  dtype: the table follows the activations
+    it is added to (float32 in the reference; float64 in the checker's float64 run)."""
     half = dim // 2
-    freq = torch.exp(torch.arange(half, dtype=torch.float) * -(math.log(10000) / (half - 1)))
-    ang = torch.arange(n, dtype=torch.float).unsqueeze(1) * freq.unsqueeze(0)
+    freq = torch.exp(torch.arange(half, dtype=dtype) * -(math.log(10000) / (half - 1)))
+    ang = torch.arange(n, dtype=dtype).unsqueeze(1) * freq.unsqueeze(0)
     emb = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1).view(n, -1)
     if dim % 2 == 1:
-        emb = torch.cat([emb, torch.zeros(n, 1)], dim=1)
+        emb = torch.cat([emb, torch.zeros(n, 1, dtype=dtype)], dim=1)
     if padding_idx is not None:
         emb[padding_idx, :] = 0
     return emb
@@ -202,7 +209,7 @@ def subsample(W, cfg, src_tokens, src_lengths, training=False, trace=None):
     x = site_act(cfg, "encoder.fc3", act)(F.linear(x, W["encoder.fc3.weight"], W["encoder.fc3.bias"]))    # :227
     if trace is not None:
         trace["fc3"] = x
-    table = sinusoid_table(T4 + 1, cfg["D"], 0)
+    table = sinusoid_table(T4 + 1, cfg["D"], 0, x.dtype)
     pos = audio_positions(lengths, T4)
     x = x + table[pos].transpose(0, 1)                                         # :229
     if cfg.get("layernorm_embedding"):                                         # :230-231 (before the dropout of :232)
@@ -240,7 +247,7 @@ def mha(W, pfx, heads, query, key, key_padding_mask=None, causal=False, dist_pen
         # modules/conv_transformer_layer.py:22-27): scores -= max(0, ln|i - j|), after the padding mask
         dist = (torch.arange(Tq).unsqueeze(1) - torch.arange(Tk).unsqueeze(0)).abs().float()
         s = s - torch.max(torch.zeros_like(dist), torch.log(dist)).unsqueeze(0)
-    p = F.softmax(s.float(), dim=-1)
+    p = F.softmax(_wide(s), dim=-1)
     if probs_out is not None:
         # need_weights / need_head_weights (multihead_attention.py:342-355): the softmax output (before dropout) as
         # (heads, B, Tq, Tk); the decoder averages the first `alignment_heads` of them (transformer.py:772-777)
@@ -300,7 +307,8 @@ def ctc_compress(W, cfg, x, lengths, pred_override=None):
             np.ascontiguousarray(np.asarray(pred_override, dtype=np.int64))         # (B,T)    :284
         runs = int_ref.ctc_rle_np(pred, lengths.numpy())                  # :285
         new_lengths = torch.tensor([len(r) for r in runs], dtype=torch.long)
-        Wm = torch.from_numpy(int_ref.compress_weights_np(prob.numpy(), runs, cfg["strategy"]))
+        Wm = torch.from_numpy(int_ref.compress_weights_np(prob.numpy(), runs, cfg["strategy"],
+                                                            np.float64 if x.dtype == torch.float64 else np.float32))
     out = x.permute(1, 2, 0).bmm(Wm).permute(2, 0, 1)                      # :290-291
     return x_ctc, out, new_lengths, torch.from_numpy(pred.astype(np.int64))
 
@@ -338,8 +346,8 @@ def decoder_forward(W, cfg, prev_output_tokens, enc_out, enc_pad_mask, pfx="deco
     pad = cfg["pad"]
     B, L = prev_output_tokens.shape
     scale = 1.0 if cfg["no_scale_embedding"] else math.sqrt(D)
-    table = sinusoid_table(pad + 1 + L, D, pad)
     x = scale * W[pfx + "embed_tokens.weight"][prev_output_tokens]           # :720
+    table = sinusoid_table(pad + 1 + L, D, pad, x.dtype)
     x = x + table[token_positions(prev_output_tokens, pad)]                   # :728-729
     if cfg.get("layernorm_embedding"):                                         # :731-732
         x = layer_norm(W, pfx + "layernorm_embedding.", x, cfg["ln_eps"])
@@ -511,7 +519,7 @@ def two_phase_beam_search(W, cfg, src_tokens, src_lengths, beam, max_len_a=0.0, 
 # ------------------------------------------------------------------ losses (a14-a16)
 def label_smoothed_nll(logits, target, eps, pad):
     """label_smoothed_cross_entropy.py:12-29 with log_softmax in fp32 (fairseq_decoder.py:58-79)."""
-    lp = F.log_softmax(logits.float(), dim=-1).view(-1, logits.shape[-1])
+    lp = F.log_softmax(_wide(logits), dim=-1).view(-1, logits.shape[-1])
     t = target.reshape(-1, 1)
     nll = -lp.gather(1, t)
     smooth = -lp.sum(dim=-1, keepdim=True)
@@ -575,7 +583,7 @@ class _CTCLoss(torch.autograd.Function):
                 occ[:, ext[s]] = np.logaddexp(occ[:, ext[s]], la[:, s] + lb[:, s])
             grad[:Tb, b, :] = np.exp(lp[:Tb, b, :]) - np.exp(occ - lp[:Tb, b, :] - ll)
         ctx.save_for_backward(torch.from_numpy(grad).to(logits.dtype))
-        return torch.tensor(total, dtype=torch.float32)
+        return torch.tensor(total, dtype=torch.float64 if logits.dtype == torch.float64 else torch.float32)
 
     @staticmethod
     def backward(ctx, g):
@@ -596,7 +604,7 @@ def ctc_branch(cfg, ctc_out, ctc_pad_mask, transcript, transcript_lengths, blank
     else:
         in_len = T - ctc_pad_mask.sum(dim=1)                         # mask is (B,T) here
     loss = ctc_loss_sum(ctc_out, transcript, in_len, transcript_lengths, blank)
-    lp = F.log_softmax(ctc_out.float(), dim=-1).transpose(0, 1)      # (B,T,V)
+    lp = F.log_softmax(_wide(ctc_out), dim=-1).transpose(0, 1)     # (B,T,V)
     pred = int_ref.argmax_first_np(lp.detach().numpy())
     err, tot = int_ref.ctc_uer_np(pred, in_len.numpy(), transcript.numpy(), transcript_lengths.numpy(), blank)
     return loss, err, tot, in_len
@@ -634,12 +642,12 @@ def kd_loss(logits, target, teacher_idx, teacher_logits, lam, tau, pad):
     mask = t.ne(pad)
     loss = logits.new_zeros(())
     if lam > 0:
-        lp = F.log_softmax((logits / tau).float(), dim=-1).view(-1, V)
+        lp = F.log_softmax(_wide(logits / tau), dim=-1).view(-1, V)
         tp = F.softmax(teacher_logits / tau, dim=-1).view(-1, teacher_logits.shape[-1])
         sel = lp.gather(1, teacher_idx.reshape(-1, teacher_idx.shape[-1]).long())
         loss = loss + lam * (-(sel * tp).sum(-1) * mask.float()).sum()
     if lam < 1:
-        lp = F.log_softmax(logits.float(), dim=-1).view(-1, V)
+        lp = F.log_softmax(_wide(logits), dim=-1).view(-1, V)
         loss = loss + (1 - lam) * F.nll_loss(lp, t, ignore_index=pad, reduction="sum")
     return loss
 

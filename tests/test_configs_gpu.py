@@ -17,14 +17,23 @@ runs at full model size on the host.  Tolerances, stated per test:
              both modes; in fp32 mode also bit-exact against the oracle's own f32 forward.  In bf16 mode the float path is compared
              with the oracle GIVEN the engine's integer path (s2t_ref.ctc_compress(pred_override=...)): an arg-max over
              bf16-rounded logits may legitimately differ from the f32 one at near-ties; the number of such frames is reported.
+  per place  the figures above are whole-tensor ones and average a lost tile away.  fp32 mode: every element of every gradient tensor, of
+             the encoder output and of the CTC logits within 1e-4 of the tensor's largest (with the ReLU decisions shared).  bf16 mode,
+             m-preset cases: every 64-row block of every gradient tensor and of the encoder output within margin x null spread of the
+             tensor's own relative error, the null spread measured once per process on the oracle against its float64 run
+             (null_spreads(), host only).  tests/grad_compare.py, tests/test_grad_compare_cpu.py; the comment above BLOCK_MARGIN.
 """
+import contextlib
+import functools
 import json
 import os
+import time
 
 import numpy as np
 import pytest
 import torch
 
+import grad_compare as gc
 from oracle import int_ref, s2t_ref
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +51,8 @@ def to_dev(s):
     return s
 
 
-def build(arch, dtype, criterion="ctc_multi_loss", seed=11, dual=False, ctc_layer=8, **over):
+def build_ref(arch, criterion="ctc_multi_loss", seed=11, dual=False, ctc_layer=8, **over):
+    """the host half of build(): arguments, task, the oracle's configuration and the weights -- nothing here touches the device"""
     from fbk_fairseq_st_amd import conv_transformer, criterions, tasks  # noqa: F401
     from fbk_fairseq_st_amd.data import Dictionary
     from fbk_fairseq_st_amd.registry import apply_arch, namespace
@@ -58,7 +68,6 @@ def build(arch, dtype, criterion="ctc_multi_loss", seed=11, dual=False, ctc_laye
     if is_ctc:
         src.add_symbol("<ctc_blank>")
     task = tasks.SpeechTranslationCTCTask(a, tgt, src)
-    model, crit = task.build_model(a), task.build_criterion(a)
     conv = eval(a.encoder_convolutions)[0][0]
     cfg = s2t_ref.default_cfg(D=a.encoder_embed_dim, heads=a.encoder_attention_heads, ffn=a.encoder_ffn_embed_dim,
                               enc_layers=a.encoder_layers, dec_layers=a.decoder_layers, ctc_layer=ctc_layer if is_ctc else 0,
@@ -72,6 +81,13 @@ def build(arch, dtype, criterion="ctc_multi_loss", seed=11, dual=False, ctc_laye
         W["encoder.ctc_fc.bias"][[7, 19, 123, 2048, 4999, blank]] += 6.0
     if "decoder.output_projection.weight" in W:
         W["decoder.output_projection.weight"][2] *= 4.0       # EOS reachable for the generation tests (as tests/golden/make_golden.py)
+    return a, task, cfg, W
+
+
+def build(arch, dtype, criterion="ctc_multi_loss", seed=11, dual=False, ctc_layer=8, **over):
+    a, task, cfg, W = build_ref(arch, criterion, seed, dual, ctc_layer, **over)
+    is_ctc = criterion == "ctc_multi_loss"
+    model, crit = task.build_model(a), task.build_criterion(a)
     model.load_state_dict({k: v for k, v in W.items() if not k.startswith("criterion.")})
     if is_ctc:
         with torch.no_grad():
@@ -101,11 +117,23 @@ def engine_grads(model):
     return fused_to_reference({n: model.arena.g(n).detach().float().cpu().clone() for n in model.arena.slices})
 
 
+# engine gradients without an oracle tensor, by name prefix: the criterion-owned CTC head (ctc_multi_loss.py:14-46) lives in the arena
+# of every ctc_multi_loss model, but with --ctc-compress-out the loss reads the encoder's own ctc_fc and that head is never run: the
+# oracle's autograd leaves its gradient None, the engine's must be exactly zero
+UNCOMPARED_GRADS = ("criterion.ctc_aware_model.fc_out.",)
+
+
 def compare_grads(mine, ref, tol, cos_min=None, what=""):
     """per-tensor gradient norms, relative; tensors whose exact gradient is zero (the key bias of an attention: softmax is
     invariant to it) hold rounding noise on both sides and are compared against a floor of 1e-6 of the largest tensor norm"""
     worst = (0.0, None)
     floor = 1e-6 * max(float(g.norm()) for g in ref.values())
+    # the reverse of the loop below: an engine gradient that no oracle tensor is compared with would be invisible
+    for k, g in mine.items():
+        if k in ref:
+            continue
+        assert k.startswith(UNCOMPARED_GRADS), "engine gradient %s has no oracle tensor to be compared with" % k
+        assert not bool(g.any()), "%s: a head this criterion never runs has a non-zero gradient" % k
     for k, g in ref.items():
         if k.endswith("_float_tensor"):
             continue
@@ -142,6 +170,7 @@ def compare_grads(mine, ref, tol, cos_min=None, what=""):
 _MEASURED_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "parity_measured.json")
 _MEASURED = json.load(open(_MEASURED_PATH)) if os.path.exists(_MEASURED_PATH) else {}
 _FLOOR = dict(grad=2e-3, one_minus_cos=1e-3, loss=3e-4, flips=0.005, gen=1e-2)
+_FLOOR.update(block=0.05)     # block_check's worst block, as a fraction of its margin: a maximum over ~2,000 blocks (atomics order)
 
 
 def tripwire(what, **figures):
@@ -195,15 +224,288 @@ TOL_BF16_DUAL = dict(loss=6e-3, grad=9e-2, cos=0.99)
 BF16_MAX_FLIP_FRACTION = 0.04
 
 
-def check_ctc_multi_loss(arch, dtype, B, T, L, lengths, seed, **over):
+# ---- per element (fp32) and per block (bf16), tests/grad_compare.py.  The whole-tensor figures of compare_grads average a localized
+# defect away (a lost 32-row tile of an fc1 weight gradient: cosine 0.9922, norm 7.8e-3; tests/test_grad_compare_cpu.py plants it).
+#   fp32   max|g - g_oracle| <= FP32_NORTH_STAR x max|g_oracle| for EVERY gradient tensor, and for the encoder output and the CTC logits
+#          on the valid frames -- in the comparison that shares the ReLU decisions (a flipped ReLU legitimately moves single elements:
+#          the free-running ReLU comparison only prints its figure); a model without ReLU has no such decision and is held directly.
+#          A tensor may leave 1e-4 only where the oracle's OWN f32-against-f64 element error on it (reference_pair(case)["elem"])
+#          exceeds a quarter of the bound; its bound is then 4 x that reference-only figure: ref_only(), stated at each test.
+#   bf16   honest noise is percent-sized on every element, so only its distribution over the tensor tells it from a defect: every block
+#          of 64 rows (1-D: 512 elements) may be wrong by at most BLOCK_MARGIN x null spread x the whole tensor's relative error, the
+#          null spread being how unevenly the oracle's own rounding (f32 against f64, same discrete decisions) falls on the blocks of
+#          the tensor of that name -- a measurement of the reference against itself.  Margin 3: the engine rounds to bf16 at points
+#          where the f32 oracle does not round at all.  A limit that lets planted defect (a) through is worth nothing, so margin x
+#          null spread is capped below what a zeroed half-block shows on a tensor of that many blocks (half_block_figure: 4.9 on the
+#          32 blocks of an fc1 weight, test_grad_compare_cpu).  With fewer than 32 blocks a lost half-block is more than 1/64 of the
+#          energy and the cosine of compare_grads is the criterion that sees it.  The cap takes the noise to be BF16_NOISE = 0.07: on a
+#          tensor whose honest r is ~0.1 AND whose null spread is 1.5 or more the block criterion would let (a) through; such a
+#          tensor's (a) has cosine 0.9922 x 0.995 = 0.987 and fails the 0.99 of compare_grads, which stays in force.
+#          Measured on an MI355X (one defect-free build, two runs): the figure r_i / (r x null spread), worst block of each tensor, over
+#          the 155 to 176 tensors of a case: median 1.000, 90 % 1.14 to 1.19.  Closest to its margin: encoder.ctc_fc.bias in the
+#          2 x 1500 case, 2.51 at block 6 = 0.84 of margin 3 (10 runs of 512 elements: no cap; the tensor of the six boosted units,
+#          whole-tensor r 4.3e-3, as the weight below) -- within 19 % of failing on the one build it has been seen on.  Then
+#          encoder.ctc_fc.weight (below), then decoder.layers.2.fc1.weight 2.07 (ragged case, 0.69 of its margin); every other
+#          tensor <= 1.72; encoder output 0.70 to 0.71.  The null spreads themselves move with the host's f32 summation order
+#          (encoder.ctc_fc.weight 1.19 on one host, 1.39 on another): they are measured where the test runs, not recorded.
+BLOCK_MARGIN = 3.0
+# tensor-name suffix -> margin, where an honest run needs more than 3:
+#   encoder.ctc_fc.weight [5001, 512]   measured 2.66 (2 x 1500), 3.57 (ragged, block 55), 3.37 (16 x 1500, block 7).  The six rows of
+#       the boosted units (build()) hold nearly all of its energy and are accurate, so the WHOLE tensor's r is 5e-3 to 8e-3, a tenth of
+#       what bf16 leaves elsewhere; a block of ordinary rows at 3.57 x 1.19 x 4.9e-3 = 2.1e-2 is an ordinary bf16 block.  The product
+#       passes its fp64 test at this exact shape (test_wgrad_group_gpu.test_bf16_ctc_head_at_the_config_shape), so the margin of the
+#       class is twice what the honest run requires, 2 x 3.57.  That 7.2 is never the effective margin: on its 79 blocks the cap makes
+#       it min(7.2, 0.95 x 6.67 / null spread) = 5.3 at null spread 1.19, so the worst honest figure, 3.57, is 0.67 of its margin.
+#       tests/test_grad_compare_cpu.py plants defect (a) into a tensor of this name and shape and sends it through block_check.
+BLOCK_MARGIN_BY_CLASS = {"encoder.ctc_fc.weight": 7.2}
+BF16_NOISE = 0.07                 # relative error bf16 storage leaves on a gradient tensor of the m preset (1 - cos ~ 2.5e-3)
+
+
+def ref_only(**figures):
+    """fp32 element bounds from the ORACLE's own error: tensor -> 4 x (the f32 oracle's element error against its float64 run on that
+    case, reference_pair(...)["elem"]), admitted only where that figure exceeds a quarter of FP32_NORTH_STAR.  Keys: c0b, c1b, c1w =
+    encoder.convolutions.{0.bias, 1.bias, 1.weight}: the end of the backward chain, sums over every (utterance, frame, mel) position
+    of a gradient whose plain sum BatchNorm's backward has just made zero -- the f32 ORACLE is the noisy side there (up to 3.4e-4 of
+    max|g| from float64 at 32 x 1000; the engine sits within 1.5e-4 of it).  The figures at the tests are host measurements of this
+    file's cases by tools/parity_reference_noise.py (16 threads; reference_pair / reference_pair_of); they move by tens of percent
+    with the host's summation order, which the factor 4 is there for.
+    The widening is by the REFERENCE's noise alone, whatever the engine measured: a 1e-4 bound against a reference that is itself
+    3e-5 to 3.4e-4 from the truth on that tensor passes or fails by the reference's rounding.  What the engine measured against the
+    f32 oracle on the one build seen (ReLU decisions shared), of the widened pairs: above 1e-4 on 32 x 1000 ragged c0b 1.47e-4 and
+    l preset c0b 1.01e-4; below it on 32 x 1000 c1b 9.8e-5, dual decoder c0b 8.8e-5, l preset c1w 7.0e-5 and c1b 4.3e-5, GELU c0b
+    6.6e-5, 3 x 1500 ragged c0b 6.3e-5, 32 x 1000 ragged c1w 5.6e-5 and c1b 3.4e-5, KD c1b 4.8e-5 and c0b 1.9e-5, dual decoder
+    c1b 1.8e-5 and c1w 1.3e-5, shared embedding c1b 1.7e-5 and c1w 7.9e-6.  element_check prints the figure of every widened pair
+    on every run.  A pair that is not widened is held at 1e-4."""
+    names = dict(c0b="encoder.convolutions.0.bias", c1b="encoder.convolutions.1.bias", c1w="encoder.convolutions.1.weight")
+    assert all(v > FP32_NORTH_STAR / 4 for v in figures.values()), figures
+    return {names[k]: 4 * v for k, v in figures.items()}
+
+
+def shared_relu_cfg(model, cfg, W):
+    """the oracle's configuration with the ReLU active sets the engine recorded in the pass just run (engine.relu_record)"""
+    masks = {k: v.cpu() for k, v in model.engine.relu_record.items()}
+    model.engine.relu_record = None
+    assert len(masks) == relu_sites(cfg, W), (sorted(masks), relu_sites(cfg, W))
+    return dict(cfg, relu_masks=masks)
+
+
+def element_check_shared_relu(model, cfg, W, run, oout, ograds, what, bounds):
+    """the fp32 element bound of a ReLU model outside check_ctc_multi_loss, on every gradient tensor and on the encoder output (valid
+    frames; these models have no CTC tap): printed for the free-running oracle run (oout, ograds), held against a second oracle run
+    `run(Wg, cfg)` that takes the engine's ReLU active sets (record_relu before the pass).  One ReLU input within f32 rounding of
+    zero, active on one side only, moves single elements by 1e-2 of max|g| (measured on the KD and dual-decoder cases:
+    decoder.layers.4.fc1.weight 1.3e-2, encoder.fc3.weight 1.5e-2): a bound on the free-running comparison would pass or fail by
+    which side of zero that input fell on."""
+    mine = engine_grads(model)
+    last = model.encoder._last
+    acts = {"encoder_out": valid_rows(last["out"].detach().float().cpu(), last["lengths_host"])}
+    element_check(mine, ograds, what + " gradients", enforce=False)
+    element_check(acts, encoder_rows(oout[-1]), what + " activations", enforce=False)
+    cfg_m = shared_relu_cfg(model, cfg, W)
+    mout, mgrads = oracle_grads(W, lambda Wg: run(Wg, cfg_m))
+    element_check(mine, mgrads, what + " gradients, ReLU decisions shared", bounds=bounds)
+    element_check(acts, encoder_rows(mout[-1]), what + " activations, ReLU decisions shared")
+
+
+def record_relu(model):
+    model._ensure_engine(DEV)
+    model.engine.relu_record = {}                       # the ReLU decisions of the next pass, for the oracle run that shares them
+
+
+def half_block_figure(n_blocks, noise=BF16_NOISE):
+    """the block figure of planted defect (a): half of one of n equal blocks zeroed, under relative noise `noise` everywhere:
+    r_i = sqrt(1/2), r = sqrt(noise^2 + 1 / (2 n))"""
+    return (0.5 / (noise ** 2 + 0.5 / n_blocks)) ** 0.5
+
+
+def valid_rows(x, lengths):
+    """[T, B, ...] -> the rows t < lengths[b], utterance after utterance: [sum(lengths), ...]"""
+    return torch.cat([x[:int(n), b] for b, n in enumerate(lengths)])
+
+
+def engine_activations(last):
+    return {"encoder_out": valid_rows(last["out"].detach().float().cpu(), last["lengths_host"]),
+            "ctc_out": valid_rows(last["ctc_out"].detach().float().cpu(), last["ctc_lengths_host"])}
+
+
+def oracle_activations(enc, ctc_lengths):
+    return {"encoder_out": valid_rows(enc.encoder_out.detach(), enc.new_lengths), "ctc_out": valid_rows(enc.ctc_out.detach(), ctc_lengths)}
+
+
+def encoder_rows(enc):
+    """a model without CTC compression: the oracle's encoder output on the valid frames"""
+    return {"encoder_out": valid_rows(enc.encoder_out.detach(), enc.src_lengths)}
+
+
+@contextlib.contextmanager
+def recorded_relu(record):
+    """record[site] = the active set (x > 0) of every ReLU site of the oracle runs inside: what `relu_masks` takes.  The oracle is
+    not changed for it: its `site_act` is wrapped for the duration."""
+    plain = s2t_ref.site_act
+
+    def site_act(cfg, site, act):
+        f = plain(cfg, site, act)
+        if cfg["act"] != "relu":
+            return f
+
+        def g(x):
+            record[site] = x.detach() > 0
+            return f(x)
+        return g
+    s2t_ref.site_act = site_act
+    try:
+        yield record
+    finally:
+        s2t_ref.site_act = plain
+
+
+def relu_sites(cfg, W):
+    """number of ReLU sites of a model: two convolutions and fc3, one per encoder layer, one per layer of every decoder"""
+    if cfg["act"] != "relu":
+        return 0
+    return 3 + cfg["enc_layers"] + cfg["dec_layers"] * sum(k.endswith("decoder.embed_tokens.weight") for k in W)
+
+
+def oracle_pair(W, cfg, run):
+    """A loss of this file through the f32 oracle and through the float64 one, on the same discrete decisions: what the f32 oracle
+    itself is measured against.  run(Wg, cfg, first=None) -> (loss, ..., EncOut); the second call gets the weights in float64, cfg
+    with the ReLU active sets the first run took (recorded_relu) and first = the first run's output: it casts its features to
+    float64 (the oracle's constants follow the input dtype) and takes whatever other decision the first run made (the CTC arg-max).
+    Returns (f32 output, f32 gradients, float64 output, float64 gradients, seconds of the two runs)."""
+    t0 = time.time()
+    with recorded_relu({}) as masks:
+        o32, g32 = oracle_grads(W, lambda Wg: run(Wg, cfg))
+    # every site, or the float64 run would take ReLU decisions of its own and the null spreads would grow without a failure
+    assert len(masks) == relu_sites(cfg, W), (sorted(masks), relu_sites(cfg, W))
+    t1 = time.time()
+    W64 = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in W.items()}
+    o64, g64 = oracle_grads(W64, lambda Wg: run(Wg, dict(cfg, relu_masks=masks), o32))
+    t2 = time.time()
+    assert o64[0].dtype == torch.float64 and all(g.dtype == torch.float64 for g in g64.values()) and sorted(g32) == sorted(g64)
+    return o32, g32, o64, g64, (t1 - t0, t2 - t1)
+
+
+def oracle_grads64(W, sample, cfg, blank, pred_override=None, relu_masks=None):
+    """s2t_ref.ctc_multi_loss with weights and features in float64; pred_override / relu_masks: the discrete decisions of an f32 run
+    (oracle_pair is the way to get both runs)"""
+    W64 = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in W.items()}
+    return oracle_grads(W64, ctc_run(sample, blank, pred_override, True, dict(cfg, relu_masks=relu_masks)))
+
+
+def ctc_run(sample, blank, pred_override=None, f64=False, cfg=None):
+    s = dict(sample, net_input=dict(sample["net_input"], src_tokens=sample["net_input"]["src_tokens"].double())) if f64 else sample
+    return lambda Wg: s2t_ref.ctc_multi_loss(Wg, cfg, s, 0.1, 1.0, blank, training=True, pred_override=pred_override)
+
+
+def null_spreads():
+    """Once per process, on the host: the Cfg3 case (m preset, B = 2, T = 1500, seed 3), reference against reference"""
+    return reference_pair("s2t_transformer_m", 2, 1500, 40, 3)
+
+
+def self_error(g32, g64, a32, a64):
+    """(null, elem) of an oracle_pair: tensor name (and activation name) -> grad_compare.spread(f32, f64), the null spread block_check
+    divides by / -> the f32 oracle's element error against float64 in units of max|g|, the arbiter of ref_only()"""
+    null, elem = {}, {}
+    for k in g64:
+        if k.endswith("k_proj.bias"):            # exactly zero in exact arithmetic: rounding noise on both sides, nothing to spread
+            continue
+        null[k], elem[k] = gc.spread(g32[k], g64[k]), gc.elementwise(g32[k], g64[k])[0]
+    for k in a64:
+        null[k], elem[k] = gc.spread(a32[k], a64[k]), gc.elementwise(a32[k], a64[k])[0]
+    return null, elem
+
+
+@functools.lru_cache(maxsize=None)
+def reference_pair(arch, B, T, L, seed, lengths=None, **over):
+    """One ctc_multi_loss case of this file through oracle_pair (`lengths`: a tuple).  Returns dict(null, elem: self_error; seconds of
+    the float64 run).  Reference against reference: the code under test is not involved."""
+    a, task, cfg, W = build_ref(arch, **over)
+    blank = task.source_dictionary.index("<ctc_blank>")
+    sample = batch(task, B, T, L, L, seed, list(lengths) if lengths else None)
+
+    def run(Wg, cfg, first=None):
+        return ctc_run(sample, blank, None if first is None else first[3].ctc_pred.numpy(), first is not None, cfg)(Wg)
+    (l32, _, _, e32, _, _), g32, (l64, _, _, e64, _, _), g64, (s32, s64) = oracle_pair(W, cfg, run)
+    assert [int(v) for v in e32.new_lengths] == [int(v) for v in e64.new_lengths]
+    len4 = [e32.ctc_out.shape[0]] * B if e32.ctc_padding_mask is None else (~e32.ctc_padding_mask).sum(1).tolist()
+    null, elem = self_error(g32, g64, oracle_activations(e32, len4), oracle_activations(e64, len4))
+    top = sorted(null.items(), key=lambda kv: -kv[1])[:4]
+    tope = sorted(elem.items(), key=lambda kv: -kv[1])[:4]
+    print("MEASURED float64 oracle (%s, %d x %d): f32 run %.1f s, float64 run %.1f s; loss %.7f against %.7f" % (arch, B, T, s32, s64, float(l32), float(l64)))
+    print("MEASURED null spread (f32 oracle against float64, per tensor): median %.3f, largest %s" %
+          (float(np.median(list(null.values()))), ", ".join("%s %.3f" % kv for kv in top)))
+    print("MEASURED f32 oracle's own element error against float64: median %.2e, largest %s" %
+          (float(np.median(list(elem.values()))), ", ".join("%s %.2e" % kv for kv in tope)))
+    return dict(null=null, elem=elem, seconds=s64)
+
+
+def reference_pair_of(build_kw, case):
+    """the same for a case given as its build() keywords and its host half (kd_case, shared_embed_case, dual_case): elem only"""
+    a, task, cfg, W = build_ref(**build_kw)
+    sample, run = case(task)
+    o32, g32, o64, g64, _ = oracle_pair(W, cfg, run)
+    return self_error(g32, g64, encoder_rows(o32[-1]), encoder_rows(o64[-1]))[1]
+
+
+def element_check(mine, ref, what, enforce=True, bounds=None):
+    """fp32: max|mine - ref| / max|ref| per tensor against FP32_NORTH_STAR (`bounds`: tensor name -> its own bound, from ref_only());
+    every figure is printed before anything is asserted.  The k_proj.bias tensors keep the rule of compare_grads (their reference
+    is zero in exact arithmetic)."""
+    bounds = bounds or {}
+    rows = []
+    for k, g in ref.items():
+        if k.endswith("_float_tensor") or k.endswith("k_proj.bias"):
+            continue
+        e, idx = gc.elementwise(mine[k], g)
+        rows.append((e / bounds.get(k, FP32_NORTH_STAR), e, k, idx))
+    rows.sort(reverse=True)
+    x, e, k, idx = rows[0]
+    print("MEASURED %s: worst element-wise error %.3e x max|oracle| (%s at %s) = %.3f of its bound%s; next %s" %
+          (what, e, k, idx, x, "" if enforce else " (printed only)", ", ".join("%s %.2e" % (r[2], r[1]) for r in rows[1:4])))
+    if bounds:
+        print("MEASURED %s: tensors whose bound follows the oracle's own error: %s" %
+              (what, ", ".join("%s %.2e (bound %.1e)" % (r[2], r[1], bounds[r[2]]) for r in rows if r[2] in bounds)))
+    if enforce:
+        over = ["%s %.3e at %s (bound %.1e)" % (r[2], r[1], r[3], bounds.get(r[2], FP32_NORTH_STAR)) for r in rows if r[0] > 1.0]
+        assert not over, "%s: element-wise error above its bound x max|oracle|: %s" % (what, "; ".join(over[:8]))
+    return rows[0]
+
+
+def block_check(mine, ref, what, select=True):
+    """bf16: the worst block of every tensor that carries signal (compare_grads' selection for the cosine: norm above 1e-3 of the
+    largest) against BLOCK_MARGIN x null spread x the tensor's own relative error; low-energy blocks by their absolute error."""
+    null = null_spreads()["null"]
+    big = 1e-3 * max(float(g.norm()) for g in ref.values()) if select else 0.0
+    rows = []
+    for k, g in ref.items():
+        if k.endswith("_float_tensor") or k.endswith("k_proj.bias") or float(g.norm()) < big:
+            continue
+        margin = next((m for sfx, m in BLOCK_MARGIN_BY_CLASS.items() if k.endswith(sfx)), BLOCK_MARGIN)
+        fig, blk, kb = gc.worst_block(mine[k], g, null.get(k, 1.0))
+        if kb["n"] >= 32:
+            margin = min(margin, 0.95 * half_block_figure(kb["n"]) / null.get(k, 1.0))
+        rows.append((fig / margin, fig, k, blk, kb["r"], null.get(k, 1.0), bool(kb["low"][blk]) if blk >= 0 else False))
+    rows.sort(reverse=True)
+    figs = np.array([r[1] for r in rows])
+    x, fig, k, blk, r, ns, low = rows[0]
+    print("MEASURED %s: worst block ratio against the null spread %.3f (%s block %d%s, tensor r %.3e, null spread %.3f) = %.3f of its "
+          "margin; over %d tensors median %.3f, 90 %% %.3f; next %s" %
+          (what, fig, k, blk, ", low-energy" if low else "", r, ns, x, len(rows), float(np.median(figs)), float(np.quantile(figs, 0.9)),
+           ", ".join("%s %.3f" % (q[2], q[1]) for q in rows[1:4])))
+    tripwire(what + " blocks", block=x)
+    over = ["%s block %d: %.3f (r %.3e, null spread %.3f)" % (q[2], q[3], q[1], q[4], q[5]) for q in rows if q[0] > 1.0]
+    assert not over, "%s: blocks wrong beyond margin x null spread x the tensor's error: %s" % (what, "; ".join(over[:8]))
+    return rows[0]
+
+
+def check_ctc_multi_loss(arch, dtype, B, T, L, lengths, seed, blocks=False, element_bounds=None, **over):
     a, task, model, crit, cfg, W = build(arch, dtype, **over)
     blank = task.source_dictionary.index("<ctc_blank>")
     sample = batch(task, B, T, L, L, seed, lengths)
     model.train(); crit.train()
     model.arena.zero_grad()
     if dtype == torch.float32:
-        model._ensure_engine(DEV)
-        model.engine.relu_record = {}                   # the ReLU decisions of this pass, for the second oracle run below
+        record_relu(model)
     loss, ss, log = crit(model, to_dev(sample))
     loss.backward()
     torch.cuda.synchronize()
@@ -241,22 +543,30 @@ def check_ctc_multi_loss(arch, dtype, B, T, L, lengths, seed, **over):
         assert float(log[k]) == float(olog[k]), k
     if dtype == torch.float32:
         assert float(log["ctc_errors"]) == float(olog["ctc_errors"])
-    worst = compare_grads(engine_grads(model), ograds, t["grad"], t["cos"], what="%s %s" % (arch, dtype))
+    mine = engine_grads(model)
+    acts = engine_activations(last)
+    worst = compare_grads(mine, ograds, t["grad"], t["cos"], what="%s %s" % (arch, dtype))
     print("%s %s: loss %.6f (oracle %.6f), worst gradient-norm error %.2e at %s, frames %s -> %s" %
           (arch, dtype, float(loss), float(oloss), worst[0], worst[1], list(len4), last["lengths_host"]))
+    if dtype == torch.float32:
+        # per element: held where the comparison holds no discrete decision (no ReLU in the model), printed where a ReLU may flip
+        free = cfg["act"] != "relu"
+        element_check(mine, ograds, "%s %s gradients" % (arch, dtype), enforce=free, bounds=element_bounds)
+        element_check(acts, oracle_activations(enc, len4), "%s %s activations" % (arch, dtype), enforce=free)
+    elif blocks:
+        block_check(mine, ograds, "%s %s" % (arch, dtype))
+        block_check(acts, {"encoder_out": valid_rows(enc.encoder_out.detach(), enc.new_lengths)}, "%s %s encoder output" % (arch, dtype), select=False)
     if dtype == torch.float32 and cfg["act"] == "relu":
         # ---- north_star's fp32 bound (1e-4) with the DISCRETE decisions taken out of the comparison: the oracle runs again with the
         # engine's own ReLU active sets (as `pred_override` does for the arg-max in bf16 mode), so a pre-activation within f32 rounding
         # of zero cannot be active on one side only; what remains is floating-point arithmetic in another summation order.  The
         # free-running comparison above stays, at 1e-3.
-        masks = {k: v.cpu() for k, v in model.engine.relu_record.items()}
-        model.engine.relu_record = None
-        n_sites = 3 + cfg["enc_layers"] + cfg["dec_layers"]
-        assert len(masks) == n_sites, (sorted(masks), n_sites)
-        cfg_m = dict(cfg, relu_masks=masks)
-        (mloss, _, _, _, _, _), mgrads = oracle_grads(W, lambda Wg: s2t_ref.ctc_multi_loss(Wg, cfg_m, sample, 0.1, 1.0, blank, training=True))
+        cfg_m = shared_relu_cfg(model, cfg, W)
+        (mloss, _, _, menc, _, _), mgrads = oracle_grads(W, lambda Wg: s2t_ref.ctc_multi_loss(Wg, cfg_m, sample, 0.1, 1.0, blank, training=True))
         assert rel(loss, mloss) <= 1e-4
-        wm = compare_grads(engine_grads(model), mgrads, FP32_NORTH_STAR, t["cos"], what="%s %s, ReLU decisions shared" % (arch, dtype))
+        wm = compare_grads(mine, mgrads, FP32_NORTH_STAR, t["cos"], what="%s %s, ReLU decisions shared" % (arch, dtype))
+        element_check(mine, mgrads, "%s %s gradients, ReLU decisions shared" % (arch, dtype), bounds=element_bounds)
+        element_check(acts, oracle_activations(menc, len4), "%s %s activations, ReLU decisions shared" % (arch, dtype))
         print("%s fp32 with shared ReLU decisions: worst gradient-norm error %.2e at %s" % (arch, wm[0], wm[1]))
 
 
@@ -264,24 +574,27 @@ def check_ctc_multi_loss(arch, dtype, B, T, L, lengths, seed, **over):
 def test_cfg2_s_fp32_32x1000():
     """BASELINE.json configs[1] at its full shape: s2t_transformer_s, 32 utterances x 1000 frames x 80 mel, fp32,
     ctc_multi_loss with compression as in examples/speech_recognition/criterions/ctc_multi_loss.py:140-168"""
-    check_ctc_multi_loss("s2t_transformer_s", torch.float32, B=32, T=1000, L=30, lengths=None, seed=12)
+    check_ctc_multi_loss("s2t_transformer_s", torch.float32, B=32, T=1000, L=30, lengths=None, seed=12, element_bounds=ref_only(c1b=1.42e-4))
 
 
 def test_cfg2_s_fp32_32x1000_ragged():
     rs = np.random.RandomState(5)
     lengths = sorted([1000] + [int(v) for v in rs.randint(300, 1000, 31)], reverse=True)
-    check_ctc_multi_loss("s2t_transformer_s", torch.float32, B=32, T=1000, L=30, lengths=lengths, seed=13)
+    check_ctc_multi_loss("s2t_transformer_s", torch.float32, B=32, T=1000, L=30, lengths=lengths, seed=13,
+                         element_bounds=ref_only(c0b=3.36e-4, c1w=1.14e-4, c1b=9.15e-5))
 
 
 # ------------------------------------------------------------------------------------------------ Cfg3
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_cfg3_m_ctc_compression_T1500(dtype):
-    check_ctc_multi_loss("s2t_transformer_m", dtype, B=2, T=1500, L=40, lengths=None, seed=3)
+    """the case null_spreads() measures: the f32 oracle is within 1.3e-5 of its float64 run on every tensor, no element bound moves"""
+    check_ctc_multi_loss("s2t_transformer_m", dtype, B=2, T=1500, L=40, lengths=None, seed=3, blocks=True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_cfg3_m_ctc_compression_ragged(dtype):
-    check_ctc_multi_loss("s2t_transformer_m", dtype, B=3, T=1500, L=40, lengths=[1500, 1210, 777], seed=4)
+    check_ctc_multi_loss("s2t_transformer_m", dtype, B=3, T=1500, L=40, lengths=[1500, 1210, 777], seed=4, blocks=True,
+                         element_bounds=ref_only(c0b=2.21e-4))
 
 
 def test_cfg3_m_bf16_gemm256_route():
@@ -295,7 +608,7 @@ def test_cfg3_m_bf16_gemm256_route():
     try:
         assert K.relu_mask_bytes(16 * 375, 2048, 512) > 0
         K.prof_reset(); K.prof_enable(1)
-        check_ctc_multi_loss("s2t_transformer_m", torch.bfloat16, B=16, T=1500, L=40, lengths=None, seed=21)
+        check_ctc_multi_loss("s2t_transformer_m", torch.bfloat16, B=16, T=1500, L=40, lengths=None, seed=21, blocks=True)
         torch.cuda.synchronize()
         fam = {f: K.prof_read(f)["launches"] for f in ("gemm256_nt", "gemm256_nn", "wgrad_group")}
     finally:
@@ -336,12 +649,17 @@ def test_cfg3_m_bf16_gemm256_route_equals_the_128_wide_route_with_dropout():
     worst = max((float((g1[k] - g0[k]).norm()) / max(float(g0[k].norm()), 1e-12), k) for k in g0 if float(g0[k].norm()) > 0)
     print("MEASURED gemm256 vs 128-wide route with dropout: identical loss %.6f, worst gradient difference %.2e (%s)" % (l1, worst[0], worst[1]))
     assert worst[0] < 1e-3, worst          # f32 atomics order in the grouped weight gradients / LayerNorm parameter sums only
+    # both routes compute the same products: a difference that sits in one place (a tile, a store tail) is a defect, and the norm of
+    # the difference above averages it over the tensor
+    elem = max((gc.elementwise(g1[k], g0[k]) + (k,) for k in g0 if float(g0[k].norm()) > 0), key=lambda e: e[0])
+    print("MEASURED gemm256 vs 128-wide route with dropout: worst element difference %.2e x max|g| (%s at %s)" % (elem[0], elem[2], elem[1]))
+    assert elem[0] < 1e-3, elem
 
 
 def test_cfg3_m_gelu_model_level():
     """--activation-fn gelu through the whole model (the GELU epilogues were only pinned at kernel level)"""
     check_ctc_multi_loss("s2t_transformer_m", torch.float32, B=2, T=600, L=20, lengths=[600, 455], seed=5, activation_fn="gelu",
-                         encoder_layers=4, decoder_layers=2, ctc_layer=2)
+                         encoder_layers=4, decoder_layers=2, ctc_layer=2, element_bounds=ref_only(c0b=6.66e-5))
 
 
 # ------------------------------------------------------------------------------------------------ Cfg4
@@ -354,13 +672,24 @@ def mustc_lengths(n, seed):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_cfg4_l_mustc_shaped_lengths(dtype):
     lengths = mustc_lengths(4, 2)
-    check_ctc_multi_loss("s2t_transformer_l", dtype, B=4, T=max(lengths), L=24, lengths=lengths, seed=6)
+    check_ctc_multi_loss("s2t_transformer_l", dtype, B=4, T=max(lengths), L=24, lengths=lengths, seed=6,
+                         element_bounds=ref_only(c0b=9.36e-5, c1w=7.65e-5, c1b=6.56e-5))
 
 
 # ------------------------------------------------------------------------------------------------ Cfg5
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
-def test_cfg5_m_knowledge_distillation(dtype):
-    a, task, model, crit, cfg, W = build("s2t_transformer_m", dtype, criterion="knowledge_distillation", kd_lambda=0.6, kd_temperature=2.0)
+# the host halves of the three cases below: build() keywords, and sample + oracle run.  run(Wg, cfg, first=None) -> (loss, ..., EncOut) as
+# oracle_pair takes it; tools/parity_reference_noise.py puts them through oracle_pair for the figures ref_only() is given.
+KD_BUILD = dict(arch="s2t_transformer_m", criterion="knowledge_distillation", kd_lambda=0.6, kd_temperature=2.0)
+SHARED_EMBED_BUILD = dict(arch="s2t_transformer_s", criterion="label_smoothed_cross_entropy", share_decoder_input_output_embed=True)
+DUAL_BUILD = dict(arch="conv_transformer_dualdecoder_big2", criterion="cross_entropy_dualdecoder", dual=True, encoder_layers=12,
+                  auxiliary_loss_weight=0.3, primary_loss_weight=0.7)
+
+
+def _cast(first):
+    return (lambda x: x) if first is None else (lambda x: x.double())
+
+
+def kd_case(task):
     sample = batch(task, 4, 1000, 30, 30, 7, lengths=[1000, 1000, 870, 640])
     g = torch.Generator().manual_seed(1)
     K = 8
@@ -368,63 +697,103 @@ def test_cfg5_m_knowledge_distillation(dtype):
     tidx[:, :, 0] = sample["target"]                               # the teacher usually ranks the reference token first
     tlog = torch.randn(4, 30, K, generator=g).sort(dim=-1, descending=True)[0] * 2.0
     sample["teacher_output"] = [tidx, tlog]
+
+    def run(Wg, cfg, first=None):
+        f, ni = _cast(first), sample["net_input"]
+        enc, _ = s2t_ref.encoder_forward(Wg, cfg, f(ni["src_tokens"]), ni["src_lengths"], training=True)
+        logits = s2t_ref.decoder_forward(Wg, cfg, ni["prev_output_tokens"], enc.encoder_out, enc.encoder_padding_mask)
+        return s2t_ref.kd_loss(logits, sample["target"], tidx, f(tlog), 0.6, 2.0, cfg["pad"]), enc
+    return sample, run
+
+
+def shared_embed_case(task):
+    sample = batch(task, 4, 600, 24, 20, 9, lengths=[600, 600, 531, 322])
+
+    def run(Wg, cfg, first=None):
+        f, ni = _cast(first), sample["net_input"]
+        enc, _ = s2t_ref.encoder_forward(Wg, cfg, f(ni["src_tokens"]), ni["src_lengths"], training=True)
+        logits = s2t_ref.decoder_forward(Wg, cfg, ni["prev_output_tokens"], enc.encoder_out, enc.encoder_padding_mask)
+        return s2t_ref.label_smoothed_nll(logits, sample["target"], 0.1, cfg["pad"]) + (enc,)
+    return sample, run
+
+
+def dual_case(task):
+    sample = batch(task, 3, 1000, 30, 26, 8, lengths=[1000, 910, 505])
+    tr = sample["transcript_target"]
+    sample["net_input"]["transcript_prev_output_tokens"] = torch.cat([torch.full((3, 1), 2, dtype=torch.long), tr[:, :-1]], 1)
+
+    def run(Wg, cfg, first=None):
+        ni = dict(sample["net_input"], src_tokens=_cast(first)(sample["net_input"]["src_tokens"]))
+        loss, log, _, _ = s2t_ref.dual_decoder_loss(Wg, cfg, dict(sample, net_input=ni), 0.1, 0.7, 0.3, training=True)
+        with torch.no_grad():                                       # dual_decoder_loss keeps its encoder output to itself: once more
+            enc, _ = s2t_ref.encoder_forward(Wg, cfg, ni["src_tokens"], ni["src_lengths"], training=True)
+        return loss, log, enc
+    return sample, run
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_cfg5_m_knowledge_distillation(dtype):
+    """fp32 element bounds that follow the f32 oracle's own error against float64 on this case (ref_only): encoder.convolutions.0.bias
+    5.87e-5, encoder.convolutions.1.bias 5.19e-5"""
+    a, task, model, crit, cfg, W = build(dtype=dtype, **KD_BUILD)
+    sample, run = kd_case(task)
     model.train(); crit.train()
     model.arena.zero_grad()
+    if dtype == torch.float32:
+        record_relu(model)
     loss, ss, log = crit(model, to_dev(sample))
     loss.backward()
-
-    def run(Wg):
-        ni = sample["net_input"]
-        enc, _ = s2t_ref.encoder_forward(Wg, cfg, ni["src_tokens"], ni["src_lengths"], training=True)
-        logits = s2t_ref.decoder_forward(Wg, cfg, ni["prev_output_tokens"], enc.encoder_out, enc.encoder_padding_mask)
-        return (s2t_ref.kd_loss(logits, sample["target"], tidx, tlog, 0.6, 2.0, cfg["pad"]),)
-    (oloss,), ograds = oracle_grads(W, run)
+    oout, ograds = oracle_grads(W, lambda Wg: run(Wg, cfg))
+    oloss = oout[0]
     t = TOL[dtype] if dtype == torch.float32 else TOL_BF16_KD
     assert ss == sample["ntokens"]
     assert rel(loss, oloss) <= t["loss"], (float(loss), float(oloss))
     compare_grads(engine_grads(model), ograds, t["grad"], t["cos"], what="kd %s" % dtype)
+    if dtype == torch.float32:
+        element_check_shared_relu(model, cfg, W, run, oout, ograds, "kd %s" % dtype, ref_only(c0b=5.87e-5, c1b=5.19e-5))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_shared_decoder_input_output_embedding(dtype):
     """--share-decoder-input-output-embed (fairseq/models/transformer.py:538,618-624): one [V, D] table serves the token look-up and
-    the output projection; its gradient is the sum of the embedding scatter and the projection's dW"""
-    a, task, model, crit, cfg, W = build("s2t_transformer_s", dtype, criterion="label_smoothed_cross_entropy",
-                                         share_decoder_input_output_embed=True)
+    the output projection; its gradient is the sum of the embedding scatter and the projection's dW.
+    fp32 element bounds that follow the f32 oracle's own error against float64 on this case (ref_only): encoder.convolutions.1.bias
+    9.27e-5, encoder.convolutions.1.weight 2.76e-5"""
+    a, task, model, crit, cfg, W = build(dtype=dtype, **SHARED_EMBED_BUILD)
     assert "decoder.output_projection.weight" not in W and "decoder.output_projection.weight" not in model.arena.slices
     sd = model.state_dict()                                         # the reference's checkpoints carry the tensor under both names
     assert torch.equal(sd["decoder.output_projection.weight"].float(), sd["decoder.embed_tokens.weight"].float())
-    sample = batch(task, 4, 600, 24, 20, 9, lengths=[600, 600, 531, 322])
+    sample, run = shared_embed_case(task)
     model.train(); crit.train()
     model.arena.zero_grad()
+    if dtype == torch.float32:
+        record_relu(model)
     loss, ss, log = crit(model, to_dev(sample))
     loss.backward()
-
-    def run(Wg):
-        ni = sample["net_input"]
-        enc, _ = s2t_ref.encoder_forward(Wg, cfg, ni["src_tokens"], ni["src_lengths"], training=True)
-        logits = s2t_ref.decoder_forward(Wg, cfg, ni["prev_output_tokens"], enc.encoder_out, enc.encoder_padding_mask)
-        return s2t_ref.label_smoothed_nll(logits, sample["target"], 0.1, cfg["pad"])
-    out, ograds = oracle_grads(W, run)
+    out, ograds = oracle_grads(W, lambda Wg: run(Wg, cfg))
     t = TOL[dtype]
     assert rel(loss, out[0]) <= t["loss"], (float(loss), float(out[0]))
     compare_grads(engine_grads(model), ograds, t["grad"], t["cos"], what="shared embed %s" % dtype)
+    if dtype == torch.float32:
+        element_check_shared_relu(model, cfg, W, run, out, ograds, "shared embed %s" % dtype, ref_only(c1b=9.27e-5, c1w=2.76e-5))
     # the embedding gradient is NOT the scatter alone: the projection's share dominates it
     assert float(ograds["decoder.embed_tokens.weight"].norm()) > 0
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_cfg5_m_dual_decoder_loss(dtype):
-    a, task, model, crit, cfg, W = build("conv_transformer_dualdecoder_big2", dtype, criterion="cross_entropy_dualdecoder",
-                                         dual=True, encoder_layers=12, auxiliary_loss_weight=0.3, primary_loss_weight=0.7)
-    sample = batch(task, 3, 1000, 30, 26, 8, lengths=[1000, 910, 505])
-    tr = sample["transcript_target"]
-    sample["net_input"]["transcript_prev_output_tokens"] = torch.cat([torch.full((3, 1), 2, dtype=torch.long), tr[:, :-1]], 1)
+    """fp32 element bounds that follow the f32 oracle's own error against float64 on this case (ref_only): encoder.convolutions.0.bias
+    3.45e-5, encoder.convolutions.1.weight 3.21e-5, encoder.convolutions.1.bias 3.07e-5"""
+    a, task, model, crit, cfg, W = build(dtype=dtype, **DUAL_BUILD)
+    sample, run = dual_case(task)
     model.train(); crit.train()
     model.arena.zero_grad()
+    if dtype == torch.float32:
+        record_relu(model)
     loss, ss, log = crit(model, to_dev(sample))
     loss.backward()
-    (oloss, olog, _, _), ograds = oracle_grads(W, lambda Wg: s2t_ref.dual_decoder_loss(Wg, cfg, sample, 0.1, 0.7, 0.3, training=True))
+    oout, ograds = oracle_grads(W, lambda Wg: run(Wg, cfg))
+    oloss, olog = oout[0], oout[1]
     t = TOL[dtype] if dtype == torch.float32 else TOL_BF16_DUAL
     assert rel(loss, oloss) <= t["loss"], (float(loss), float(oloss))
     for k in ("primary_loss", "auxiliary_loss", "primary_nll_loss", "auxiliary_nll_loss"):
@@ -432,6 +801,8 @@ def test_cfg5_m_dual_decoder_loss(dtype):
     print("MEASURED dual %s: loss error %.3e" % (dtype, rel(loss, oloss)))
     tripwire("dual %s loss" % dtype, loss=rel(loss, oloss))
     compare_grads(engine_grads(model), ograds, t["grad"], t["cos"], what="dual %s" % dtype)
+    if dtype == torch.float32:
+        element_check_shared_relu(model, cfg, W, run, oout, ograds, "dual %s" % dtype, ref_only(c0b=3.45e-5, c1w=3.21e-5, c1b=3.07e-5))
 
 
 def test_cfg5_m_beam5_generation():

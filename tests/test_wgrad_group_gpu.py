@@ -329,6 +329,16 @@ def test_bf16_one_264x264_whole_and_cut(tokens, placement):
         named(BF, wgrad_lists.one_264x264(tokens), placement, db=lambda k: True, seed=tokens, poison=math.inf if tokens & 1 else math.nan).run("one_264x264 %d" % tokens)
 
 
+def test_bf16_ctc_head_at_the_config_shape():
+    """encoder.ctc_fc of the m preset at the ragged Cfg3 batch (tests/test_configs_gpu.py: 5,001 units x 512, 3 x 375 = 1,125 tokens,
+    dense in the arena, with its bias): 5,001 rows are a multiple of no tile (137 past 19 x 256, 9 past 39 x 128), 18 K-tiles, the
+    last a ragged one; element by element against fp64.  The block-wise parity criterion of the config tests gives this tensor's
+    class a wider margin and rests that on this product being right.  This is the ragged case's token count alone: the same tensor
+    at the 16 x 1500 route (6,000 tokens) is not run here."""
+    for kind in ("int", "normal"):
+        one(BF, 5001, 512, 1125, "dense", True, math.nan, kind, 5001).run("ctc head %s" % kind)
+
+
 def test_bf16_db_comes_from_the_first_column_tile_only():
     """db of a product of several column tiles is summed by tile (.., 0) alone.  In a list of one the column tiles run side by side
     and their plain read-modify-writes of db would collide into the right value; here tiles (0, 1) and (0, 2) of the last product
