@@ -937,6 +937,66 @@ def bleu_stats(hyp, hyp_len, ref, ref_len, pad, eos, unk=-1, ref_row=None):
     return stats, status
 
 
+MBR_MAX_LEN = 1024                # S2T_MBR_MAX_LEN of include/s2t_hip.h: the padded widths of s2t_bleu_pairs
+MBR_MAX_LIST = 256                # S2T_MBR_MAX_LIST: pseudo-references per sentence
+MBR_WAVE_LEN = 64                 # S2T_MBR_WAVE_LEN: candidates up to this padded width take one wave each, wider ones a workgroup
+MBR_GROUP_LEN = 256               # S2T_MBR_GROUP_LEN: of 256 threads up to this width, of 1,024 above
+MBR_SLICE = 8                     # S2T_MBR_SLICE: the entries of a candidate's list one workgroup takes
+MBR_CHUNK_BYTES = 32768           # S2T_MBR_CHUNK_BYTES: the LDS a workgroup fills with pseudo-references between two barriers
+
+
+def bleu_pairs_chunk(Pmax, wide):
+    """S2T_MBR_CHUNK: the pseudo-references of padded width Pmax a workgroup of s2t_bleu_pairs stages at once; wide: tokens are
+    staged as 64-bit (either side int64)"""
+    return min(MBR_CHUNK_BYTES // ((Pmax + 4) * (8 if wide else 4)), MBR_SLICE)
+
+
+def bleu_pairs(cand, cand_len, cand_sent, ref, ref_len, ref_off, pad, eos, unk=-1, max_list=None):
+    """BLEU statistics of every candidate row of cand [Rc, Hmax] (first cand_len[c] entries) against every pseudo-reference of its
+    sentence: cand_sent int32 [Rc] names the sentence, the rows ref_off[b] .. ref_off[b+1] - 1 of ref [Rr, Pmax] (ref_off int32
+    [B + 1]) are sentence b's list.  include/s2t_hip.h s2t_bleu_pairs; the rule of a pair is s2t_bleu_stats's with the candidate as
+    the hypothesis.  cand and ref may be the same tensor.  max_list: the widest list M, which the caller knows from its lists'
+    shapes; None reads it from ref_off (a host read).  Returns device tensors (stats int32 [Rc, M, 10], status int32 [Rc, M]: 0 done,
+    2 refused -- a length outside its padded width, a sentence outside [0, B), offsets that descend, leave [0, Rr] or span more than
+    M rows; zeros, and zeros behind a sentence's list)."""
+    ints = (torch.int32, torch.int64)
+    if cand.dim() != 2 or ref.dim() != 2 or cand.dtype not in ints or ref.dtype not in ints:
+        raise ValueError("bleu_pairs: cand and ref must be int32 / int64 [rows, width], got %s %s and %s %s"
+                         % (cand.dtype, tuple(cand.shape), ref.dtype, tuple(ref.shape)))
+    Rc, Hmax, Rr, Pmax = cand.shape[0], cand.shape[1], ref.shape[0], ref.shape[1]
+    if tuple(cand_len.shape) != (Rc,) or cand_len.dtype != cand.dtype or tuple(ref_len.shape) != (Rr,) or ref_len.dtype != ref.dtype:
+        raise ValueError("bleu_pairs: cand_len must be [%d] and ref_len [%d] in the dtype of their tokens, got %s %s and %s %s"
+                         % (Rc, Rr, cand_len.dtype, tuple(cand_len.shape), ref_len.dtype, tuple(ref_len.shape)))
+    if tuple(cand_sent.shape) != (Rc,) or cand_sent.dtype != torch.int32:
+        raise ValueError("bleu_pairs: cand_sent must be int32 [%d], got %s %s" % (Rc, cand_sent.dtype, tuple(cand_sent.shape)))
+    if ref_off.dim() != 1 or ref_off.shape[0] < 1 or ref_off.dtype != torch.int32:
+        raise ValueError("bleu_pairs: ref_off must be int32 [sentences + 1], got %s %s" % (ref_off.dtype, tuple(ref_off.shape)))
+    B = ref_off.shape[0] - 1
+    if Hmax > MBR_MAX_LEN or Pmax > MBR_MAX_LEN:
+        raise ValueError("bleu_pairs: padded widths of at most %d (S2T_MBR_MAX_LEN), got %d and %d" % (MBR_MAX_LEN, Hmax, Pmax))
+    if max_list is None:
+        max_list = int((ref_off[1:] - ref_off[:-1]).clamp(min=0, max=MBR_MAX_LIST).max()) if B else 0
+    M = int(max_list)
+    if not 0 <= M <= MBR_MAX_LIST:
+        raise ValueError("bleu_pairs: lists of at most %d pseudo-references (S2T_MBR_MAX_LIST), got %d" % (MBR_MAX_LIST, M))
+    pad, eos, unk = int(pad), int(eos), int(unk)
+    if pad == eos or (unk >= 0 and unk in (pad, eos)):
+        raise ValueError("bleu_pairs: pad, eos and unk must be three different ids, got %d, %d and %d" % (pad, eos, unk))
+    dev = cand.device
+    stats = torch.empty((Rc, M, 10), dtype=torch.int32, device=dev)      # the kernel writes every element
+    status = torch.empty((Rc, M), dtype=torch.int32, device=dev)
+    if Rc == 0 or M == 0:
+        return stats, status
+    cand, cand_len, ref, ref_len = cand.contiguous(), cand_len.contiguous(), ref.contiguous(), ref_len.contiguous()
+    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read
+    fill = torch.zeros((2,), dtype=torch.int64, device=dev)
+    p = lambda t: L.ptr(t if t.numel() else fill)
+    L.check(_lib().s2t_bleu_pairs(p(cand), L.ptr(cand_len), cand.element_size(), p(ref), p(ref_len), ref.element_size(),
+                                  L.ptr(cand_sent.contiguous()), L.ptr(ref_off.contiguous()), Rc, B, Hmax, Pmax, Rr, M, pad, eos, unk,
+                                  L.ptr(stats), L.ptr(status), L.stream()), "s2t_bleu_pairs")
+    return stats, status
+
+
 FBANK_MAX_BINS = 128              # S2T_FBANK_MAX_BINS of include/s2t_hip.h
 FBANK_TILE_ELEMS = 8192           # S2T_FBANK_TILE_ELEMS: a workgroup takes FBANK_TILE_ELEMS // N consecutive frames
 FBANK_FFT_SIZES = (256, 512, 1024)

@@ -527,6 +527,46 @@ int s2t_edit_align(const void* a, const void* a_len, int a_elem, const void* b, 
 int s2t_bleu_stats(const void* hyp, const void* hyp_len, int hyp_elem, const void* ref, const void* ref_len, int ref_elem,
                    const int* ref_row, int B, int Hmax, int Rmax, int Rrows, long long pad, long long eos, long long unk,
                    int* stats, int* status, void* stream);
+/* ---- BLEU statistics of every candidate against every pseudo-reference of its sentence (csrc/bleu_pairs.hip): the pairwise step of
+ * minimum-Bayes-risk selection over n-best lists.  The rule of a pair is s2t_bleu_stats's, above, with the candidate as the
+ * hypothesis and the pseudo-reference as the reference (trim, clipped matches, a reference-side `unk` matches nothing, an all-pad
+ * side has length 0, tokens int32 or int64 per side compared as 64-bit integers); it is not restated here.
+ * Operands: cand [Rc][Hmax] with cand_len [Rc] and ref [Rr][Pmax] with ref_len [Rr] (lengths in the dtype of their tokens);
+ * cand_sent int32 [Rc], the sentence of each candidate row; ref_off int32 [B + 1], the pseudo-references of sentence b are the rows
+ * ref_off[b] .. ref_off[b+1] - 1 of ref.  cand and ref may be the same matrix (hypotheses against themselves): nothing is copied or
+ * repeated.  M is the call's widest list; the caller states it (it knows the lists' shapes), the kernel reads no list beyond it.
+ * Outputs: stats [Rc][M][10] int32 in the order of s2t_bleu_stats (reflen = the pseudo-reference's trimmed length, predlen = the
+ * candidate's), status [Rc][M] int32, 0 for done and 2 for refused.  Every element of both is written: no initialisation is needed.
+ * Behind a sentence's list (k >= its length) stats and status are 0.  Refused, with zeros, beside ordinary pairs that are unaffected:
+ *   - a pair whose pseudo-reference length lies outside [0, Pmax];
+ *   - every pair of a candidate whose length lies outside [0, Hmax];
+ *   - all M entries of a candidate whose cand_sent lies outside [0, B), or whose sentence's offsets descend, leave [0, Rr] or span
+ *     more than M rows: such a row has no list to be behind of.
+ * Kernel: one launch, one candidate position per thread, no atomics, no host read, no memset; a pair's result does not depend on
+ * the batch around it.  A workgroup takes one candidate row and a slice of S2T_MBR_SLICE entries of its list (a candidate with one
+ * workgroup for its whole list leaves most of the chip idle at the sizes lists have: measured); one wave per candidate
+ * for Hmax <= S2T_MBR_WAVE_LEN, 256 threads up to S2T_MBR_GROUP_LEN, 1,024 threads up to S2T_MBR_MAX_LEN.  The candidate is trimmed
+ * and staged in LDS once per workgroup and every position counts the earlier positions that hold its n-grams once; the counts stay
+ * in registers.  Then the workgroup walks its slice in chunks of S2T_MBR_CHUNK(Pmax, bytes per staged token) pseudo-references --
+ * the whole slice unless the rows are wide: a chunk is staged in LDS behind one barrier, every position counts the positions of each
+ * staged pseudo-reference that hold its n-grams, and the matches are summed over the workgroup behind a second barrier.  Tokens
+ * are staged as 32-bit when both sides are int32 and as 64-bit otherwise.
+ * Refusals, before anything is launched: S2T_OK at once for Rc <= 0 or M == 0; S2T_EINVAL for a NULL required pointer (cand,
+ * cand_len, ref, ref_len, cand_sent, ref_off, stats, status), a negative width, B, Rr or M, an element size other than 4 or 8,
+ * pad == eos, or unk >= 0 equal to pad or eos; S2T_ENOTSUP for a width above S2T_MBR_MAX_LEN or M above S2T_MBR_MAX_LIST.  (The
+ * widths cover translation hypotheses; the 4,095 of s2t_bleu_stats serve document-length references, which a list of hypotheses does
+ * not have.) */
+#define S2T_MBR_MAX_LEN 1024
+#define S2T_MBR_MAX_LIST 256
+#define S2T_MBR_WAVE_LEN 64
+#define S2T_MBR_GROUP_LEN 256
+#define S2T_MBR_SLICE 8
+#define S2T_MBR_CHUNK_BYTES 32768
+#define S2T_MBR_CHUNK(Pmax, elem) \
+    (S2T_MBR_CHUNK_BYTES / (((Pmax) + 4) * (elem)) > S2T_MBR_SLICE ? S2T_MBR_SLICE : S2T_MBR_CHUNK_BYTES / (((Pmax) + 4) * (elem)))
+int s2t_bleu_pairs(const void* cand, const void* cand_len, int cand_elem, const void* ref, const void* ref_len, int ref_elem,
+                   const int* cand_sent, const int* ref_off, int Rc, int B, int Hmax, int Pmax, int Rr, int M, long long pad,
+                   long long eos, long long unk, int* stats, int* status, void* stream);
 /* ---- Kaldi log-mel filterbanks of waveforms (csrc/fbank.hip): torchaudio.compliance.kaldi.fbank with its defaults, restated.
  * Frames: W samples long, S apart, N the next power of two >= W.  An utterance of n samples has m = 0 frames if n < W, else
  * m = 1 + (n - W) / S (snip-edges); frame t is the samples [t*S, t*S + W).  No sample at or behind n is read into a result.
