@@ -997,6 +997,72 @@ def bleu_pairs(cand, cand_len, cand_sent, ref, ref_len, ref_off, pad, eos, unk=-
     return stats, status
 
 
+CHRF_MAX_LEN = 1024               # S2T_CHRF_MAX_LEN of include/s2t_hip.h: the padded widths of s2t_chrf_stats, in tokens
+CHRF_MAX_CHARS = 4095             # S2T_CHRF_MAX_CHARS: characters per side; a longer side is refused by the kernel (status 2)
+CHRF_GROUP_LEN = 64               # S2T_CHRF_GROUP_LEN: hypotheses up to this padded width take 256 threads a pair, wider ones 1,024
+CHRF_MAX_CHAR_ORDER = 6           # S2T_CHRF_MAX_CHAR_ORDER
+CHRF_MAX_WORD_ORDER = 2           # S2T_CHRF_MAX_WORD_ORDER
+CHRF_SEP = 0xffffffff             # S2T_CHRF_SEP: the word break inside a piece
+CHRF_STATS = 24                   # (hyp, ref, match) of the character orders 1 .. 6, then of the word orders 1 .. 2
+
+
+def chrf_stats(hyp, hyp_len, ref, ref_len, pieces, piece_off, unk=-1, char_order=6, word_order=0, hyp_row=None, ref_row=None):
+    """chrF statistics of pairs of token rows, hyp [Hrows, Hmax] (first hyp_len[r] entries) against ref [Rrows, Rmax]: include/s2t_hip.h
+    s2t_chrf_stats states the rule.  Tokens int32 or int64 per side, a side's lengths in its tokens' dtype.  pieces (int32 or uint32
+    code points, CHRF_SEP -- as int32, -1 -- for a word break) and piece_off (int32 [V + 2], entry V the reference-side rendering of
+    unk) are the piece table of chrf_scorer.piece_table, on the device.  hyp_row / ref_row: int32 [P], pair p is row hyp_row[p]
+    against row ref_row[p]; None means row p (without any map both sides have P rows).  Returns device tensors (stats int32 [P, 24]
+    = hyp_n, ref_n, match_n of the character orders 1 .. 6 and the word orders 1 .. 2, zeros above the configured orders; status
+    int32 [P], 0 done / 2 refused: a map entry outside its matrix, a length outside its padded width, a token outside [0, V), a side
+    of more than CHRF_MAX_CHARS characters; the stats are zeros)."""
+    ints = (torch.int32, torch.int64)
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.dtype not in ints or ref.dtype not in ints:
+        raise ValueError("chrf_stats: hyp and ref must be int32 / int64 [rows, width], got %s %s and %s %s"
+                         % (hyp.dtype, tuple(hyp.shape), ref.dtype, tuple(ref.shape)))
+    Hrows, Hmax, Rrows, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[0], ref.shape[1]
+    if tuple(hyp_len.shape) != (Hrows,) or hyp_len.dtype != hyp.dtype or tuple(ref_len.shape) != (Rrows,) or ref_len.dtype != ref.dtype:
+        raise ValueError("chrf_stats: hyp_len must be [%d] and ref_len [%d] in the dtype of their tokens, got %s %s and %s %s"
+                         % (Hrows, Rrows, hyp_len.dtype, tuple(hyp_len.shape), ref_len.dtype, tuple(ref_len.shape)))
+    for name, m in (("hyp_row", hyp_row), ("ref_row", ref_row)):
+        if m is not None and (m.dim() != 1 or m.dtype != torch.int32):
+            raise ValueError("chrf_stats: %s must be int32 [pairs], got %s %s" % (name, m.dtype, tuple(m.shape)))
+    P = hyp_row.shape[0] if hyp_row is not None else ref_row.shape[0] if ref_row is not None else Hrows
+    if (hyp_row is not None and hyp_row.shape[0] != P) or (ref_row is not None and ref_row.shape[0] != P):
+        raise ValueError("chrf_stats: hyp_row and ref_row must both be int32 [%d], got %s and %s" % (P, tuple(hyp_row.shape), tuple(ref_row.shape)))
+    if (hyp_row is None and Hrows != P) or (ref_row is None and Rrows != P):
+        raise ValueError("chrf_stats: %d pairs of %d hypothesis rows and %d reference rows need a row map for the side that has not %d rows"
+                         % (P, Hrows, Rrows, P))
+    if Hmax > CHRF_MAX_LEN or Rmax > CHRF_MAX_LEN:
+        raise ValueError("chrf_stats: padded widths of at most %d tokens (S2T_CHRF_MAX_LEN), got %d and %d" % (CHRF_MAX_LEN, Hmax, Rmax))
+    char_order, word_order, unk = int(char_order), int(word_order), int(unk)
+    if not 1 <= char_order <= CHRF_MAX_CHAR_ORDER:
+        raise ValueError("chrf_stats: char_order from 1 to %d (S2T_CHRF_MAX_CHAR_ORDER), got %d" % (CHRF_MAX_CHAR_ORDER, char_order))
+    if not 0 <= word_order <= CHRF_MAX_WORD_ORDER:
+        raise ValueError("chrf_stats: word_order from 0 to %d (S2T_CHRF_MAX_WORD_ORDER), got %d" % (CHRF_MAX_WORD_ORDER, word_order))
+    if pieces.dim() != 1 or pieces.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or piece_off.dim() != 1 or piece_off.dtype != torch.int32 \
+            or piece_off.shape[0] < 2:
+        raise ValueError("chrf_stats: the piece table is pieces (int32 / uint32 [n]) and piece_off (int32 [V + 2]), got %s %s and %s %s"
+                         % (pieces.dtype, tuple(pieces.shape), piece_off.dtype, tuple(piece_off.shape)))
+    V = piece_off.shape[0] - 2
+    if unk >= V:
+        raise ValueError("chrf_stats: unk must be a token of the table's %d (or negative), got %d" % (V, unk))
+    dev = hyp.device
+    stats = torch.empty((P, CHRF_STATS), dtype=torch.int32, device=dev)      # the kernel writes every element
+    status = torch.empty((P,), dtype=torch.int32, device=dev)
+    if P == 0:
+        return stats, status
+    hyp, hyp_len, ref, ref_len = hyp.contiguous(), hyp_len.contiguous(), ref.contiguous(), ref_len.contiguous()
+    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read
+    fill = torch.zeros((2,), dtype=torch.int64, device=dev)
+    p = lambda t: L.ptr(t if t.numel() else fill)
+    L.check(_lib().s2t_chrf_stats(p(hyp), p(hyp_len), hyp.element_size(), p(ref), p(ref_len), ref.element_size(),
+                                  L.ptr(hyp_row.contiguous()) if hyp_row is not None else 0,
+                                  L.ptr(ref_row.contiguous()) if ref_row is not None else 0, P, Hmax, Rmax, Hrows, Rrows,
+                                  p(pieces.contiguous()), L.ptr(piece_off.contiguous()), pieces.shape[0], V, unk, char_order, word_order,
+                                  L.ptr(stats), L.ptr(status), L.stream()), "s2t_chrf_stats")
+    return stats, status
+
+
 FBANK_MAX_BINS = 128              # S2T_FBANK_MAX_BINS of include/s2t_hip.h
 FBANK_TILE_ELEMS = 8192           # S2T_FBANK_TILE_ELEMS: a workgroup takes FBANK_TILE_ELEMS // N consecutive frames
 FBANK_FFT_SIZES = (256, 512, 1024)

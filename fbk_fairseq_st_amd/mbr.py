@@ -14,6 +14,9 @@ pseudo-references are the candidates themselves (`pseudo` is `hypos`, and always
 its pseudo-references: nothing is left out.  A hypothesis that contains `unk` therefore scores below 100 against itself -- a
 reference-side `unk` matches nothing: that is the reference's rule for references, kept as it is.
 
+With `utility=ChrfScorer(...)` the utility of a pair is instead the chrF of the two detokenised texts (chrf_scorer.py):
+the pairs of a sentence go through `ChrfScorer.score_pairs` on two device row maps, and `mbr_score` is in chrF percent.
+
 The hot path is csrc/bleu_pairs.hip (kernels.bleu_pairs; include/s2t_hip.h states the operands, the rule is s2t_bleu_stats's): one
 launch for all pairs of a call, no copies of the lists, no host read.  Padded widths of at most MAX_LEN tokens, lists of at most
 MAX_LIST pseudo-references per sentence.
@@ -28,6 +31,7 @@ MAX_LIST = K.MBR_MAX_LIST               # S2T_MBR_MAX_LIST
 OUTPUT_LIMIT = 1 << 30                  # bytes of stats and status one kernel call may ask for: above it a batch is cut by sentences
 STATUS = {0: "done", 2: "refused: a length outside the padded width, a sentence outside the batch, or offsets that are no list"}
 _INTS = (torch.int32, torch.int64)
+_CHRF_PAIR_BYTES = 4 * K.CHRF_STATS + 4 + 8 + 8      # stats, status, the two row maps and the float64 score of a pair of the chrF utility
 
 
 class MBRDecoder:
@@ -37,10 +41,15 @@ class MBRDecoder:
       "uniform"  every pseudo-reference counts the same;
       "score"    pseudo-reference k counts exp(score_k - max score of its sentence), computed in float64 on the device;
       a tensor or list [M] of non-negative numbers: pseudo-reference k of every sentence counts weights[k]; or one such sequence
-      per sentence (a list of them, or a tensor [B, M]), each at least as long as the sentence's list."""
+      per sentence (a list of them, or a tensor [B, M]), each at least as long as the sentence's list.
+    utility: None for the sentence BLEU over token ids described above, or a `ChrfScorer`: then the utility of a pair is the
+    scorer's `sentence_chrf` of the two texts (chrf_scorer.py; its `score_pairs` on two device row maps built from the lists'
+    shapes, one launch of kernels.chrf_stats per cut), `mbr_score` is in chrF percent, and the pairs the kernel refuses count for
+    nothing.  The scorer's accumulator takes the pairs' sums as with any `score_pairs` call."""
 
-    def __init__(self, generator, pad, eos, unk=-1, weights="uniform"):
+    def __init__(self, generator, pad, eos, unk=-1, weights="uniform", utility=None):
         self.generator = generator
+        self.utility = utility
         self.pad, self.eos, self.unk = int(pad), int(eos), int(unk)
         if self.pad == self.eos or (self.unk >= 0 and self.unk in (self.pad, self.eos)):
             raise ValueError("MBRDecoder: pad, eos and unk must be three different ids, got %d, %d and %d" % (self.pad, self.eos, self.unk))
@@ -49,8 +58,8 @@ class MBRDecoder:
         self.weights = weights
 
     @classmethod
-    def for_dictionary(cls, generator, tgt_dict, weights="uniform"):
-        return cls(generator, tgt_dict.pad(), tgt_dict.eos(), tgt_dict.unk(), weights=weights)
+    def for_dictionary(cls, generator, tgt_dict, weights="uniform", utility=None):
+        return cls(generator, tgt_dict.pad(), tgt_dict.eos(), tgt_dict.unk(), weights=weights, utility=utility)
 
     # ------------------------------------------------------------------ the generator's place
     @torch.no_grad()
@@ -80,7 +89,7 @@ class MBRDecoder:
         weights = self.weights if weights is None else weights
         dev = next((h["tokens"].device for hs in list(hypos) + list(pseudo) for h in hs), torch.device("cpu"))
         out = [[] for _ in range(B)]
-        for b0, b1 in self.chunk_sentences(nc, nr):
+        for b0, b1 in self.chunk_sentences(nc, nr, 44 if self.utility is None else _CHRF_PAIR_BYTES):
             gain = self._gains(hypos[b0:b1], pseudo[b0:b1], same, weights, b0, B, dev)
             if gain is None:
                 continue
@@ -101,13 +110,14 @@ class MBRDecoder:
         return out
 
     @staticmethod
-    def chunk_sentences(nc, nr):
-        """nc, nr: candidates and pseudo-references per sentence.  -> ranges [b0, b1) of sentences, in order, each as long as the
-        stats and status of one call stay under OUTPUT_LIMIT (a sentence that passes it alone is a range of its own)"""
+    def chunk_sentences(nc, nr, pair_bytes=44):
+        """nc, nr: candidates and pseudo-references per sentence; pair_bytes: what a call writes per pair.  -> ranges [b0, b1) of
+        sentences, in order, each as long as the stats and status of one call stay under OUTPUT_LIMIT (a sentence that passes it
+        alone is a range of its own)"""
         ranges, b0, rows, width = [], 0, 0, 0
         for b in range(len(nc)):
             r, w = rows + nc[b], max(width, nr[b])
-            if b > b0 and r * w * 44 > OUTPUT_LIMIT:
+            if b > b0 and r * w * pair_bytes > OUTPUT_LIMIT:
                 ranges.append((b0, b))
                 b0, r, w = b, nc[b], nr[b]
             rows, width = r, w
@@ -131,6 +141,8 @@ class MBRDecoder:
             off.append(off[-1] + n)
         ref_off = torch.tensor(off, dtype=torch.int32, device=dev)
         w = self._weights(weights, pseudo, nr, b0, B, dev)
+        if self.utility is not None:
+            return self._expected_utility(cand, cand_len, cand_sent, nc, ref, ref_len, ref_off, nr, w, dev)
         return self.expected_bleu(cand, cand_len, cand_sent, ref, ref_len, ref_off, weights=w, max_list=max(nr))["gain"]
 
     @staticmethod
@@ -164,6 +176,35 @@ class MBRDecoder:
         if sum(nr) == 0:
             return torch.zeros((0,), dtype=torch.float64, device=dev)
         return torch.cat([r[:n].to(dev) for r, n in zip(rows, nr)])
+
+    def _expected_utility(self, cand, cand_len, cand_sent, nc, ref, ref_len, ref_off, nr, weights, dev):
+        """the gains under `self.utility`: every pair of a sentence through score_pairs, then the weighted mean per candidate.  The
+        two row maps come from the lists' shapes (nc, nr) by device arithmetic: no host read"""
+        Rc, M = cand.shape[0], max(nr + [0])
+        total = sum(c * r for c, r in zip(nc, nr))
+        gain = torch.zeros((Rc,), dtype=torch.float64, device=dev)
+        if total == 0:
+            return gain
+        sent = cand_sent.long()
+        lo = ref_off.long()[:-1][sent]                                          # the first pseudo-reference row of each candidate
+        n = (ref_off.long()[1:] - ref_off.long()[:-1])[sent]                    # and how many it has
+        first = torch.cumsum(n, 0) - n                                          # the candidate's first pair
+        hyp_row = torch.repeat_interleave(torch.arange(Rc, device=dev), n, output_size=total)
+        k = torch.arange(total, device=dev) - first[hyp_row]                    # the pair's place in its candidate's list
+        ref_row = lo[hyp_row] + k
+        got = self.utility.score_pairs(cand, cand_len, hyp_row.int(), ref, ref_len, ref_row.int())
+        utility = torch.zeros((Rc, M), dtype=torch.float64, device=dev)
+        counts = torch.zeros((Rc, M), dtype=torch.bool, device=dev)
+        utility[hyp_row, k] = got["sentence_chrf"]
+        counts[hyp_row, k] = got["status"] == 0
+        if weights is None:
+            w = counts.double()
+        else:
+            wk = torch.zeros((Rc, M), dtype=torch.float64, device=dev)
+            wk[hyp_row, k] = weights[ref_row]
+            w = torch.where(counts, wk, torch.zeros_like(wk))
+        mass = w.sum(1)
+        return torch.where(mass > 0, (w * utility).sum(1) / torch.where(mass > 0, mass, torch.ones_like(mass)), gain)
 
     # ------------------------------------------------------------------ matrices
     @torch.no_grad()

@@ -567,6 +567,53 @@ int s2t_bleu_stats(const void* hyp, const void* hyp_len, int hyp_elem, const voi
 int s2t_bleu_pairs(const void* cand, const void* cand_len, int cand_elem, const void* ref, const void* ref_len, int ref_elem,
                    const int* cand_sent, const int* ref_off, int Rc, int B, int Hmax, int Pmax, int Rr, int M, long long pad,
                    long long eos, long long unk, int* stats, int* status, void* stream);
+/* ---- chrF / chrF++ statistics of detokenised token rows (csrc/chrf_stats.hip): per pair of rows the character n-gram totals and
+ * clipped matches of the orders 1 to 6 and the word n-gram ones of the orders 1 and 2, from which chrF (Popovic 2015, 2017; the
+ * rule sacrebleu's CHRF applies to whitespace-split text) follows.  Compatibility is by this restated rule, not by
+ * a captured fixture.
+ * Text of a row: token id t maps to the piece pieces[piece_off[t] .. piece_off[t + 1]), uint32 code points in which the value
+ * S2T_CHRF_SEP marks a word break.  The text is the concatenation of the pieces of the row's first `len` tokens; runs of SEP,
+ * leading and trailing ones included, act as one break and no SEP stays in the character stream.  piece_off has V + 2 entries:
+ * entry V is what a reference-side token equal to `unk` maps to (unk < 0: no special rendering; the hypothesis side always takes
+ * entry unk).  The host builds the table (chrf_scorer.piece_table): pad, eos and bos have empty pieces.
+ * Characters: with h and r the two streams, for n = 1 .. char_order: hyp_n = max(|h| - n + 1, 0), ref_n likewise, and
+ * match_n = the sum over distinct n-grams g of min(occurrences in h, occurrences in r).
+ * Words: the maximal SEP-free runs.  A word of one character stays whole; otherwise, if its last character is one of the 32 ASCII
+ * punctuation characters (Python's string.punctuation) it becomes two words, all but the last character and the last; otherwise,
+ * if its first character is one of them, the first and the rest; otherwise it stays whole.  Word n-grams for n = 1 .. word_order
+ * are counted and clipped the same way; two words are equal iff their code points are.
+ * Everything is an exact integer: n-grams and words are compared element by element, never by a hash.
+ * Operands: hyp [Hrows][Hmax] and ref [Rrows][Rmax], int32 or int64 tokens per side (hyp_elem, ref_elem: 4 or 8), lengths in the
+ * tokens' dtype.  hyp_row / ref_row: int32 [P] or NULL; pair p is row hyp_row[p] against row ref_row[p], NULL means row p (then the
+ * side has P rows).  Nothing is copied or repeated; one matrix may serve both sides.  n_pieces: the elements of `pieces`.
+ * Outputs: stats [P][24] int32 -- (hyp_n, ref_n, match_n) for the character orders 1 .. 6, then the word orders 1 .. 2; the orders
+ * above the configured ones are zeros -- and status [P] int32, 0 done or 2 refused.  A pair is refused, with zeros, beside ordinary
+ * pairs that are unaffected, for a map entry outside its matrix, a length outside [0, padded width], a token outside [0, V) inside
+ * a length, offsets of a piece that descend or leave [0, n_pieces], or a side of more than S2T_CHRF_MAX_CHARS characters.  Every
+ * element of both outputs is written: no initialisation is needed.
+ * Kernel: one launch, one pair per workgroup, no atomics, no host read, no memset; a pair's result does not depend on the batch
+ * around it.  Piece lengths are prefix-summed over the row, the code points expanded into LDS, and matches counted position by
+ * position as in s2t_bleu_stats (position i matches at order n iff the earlier hypothesis positions with its n-gram are fewer than
+ * the reference positions with it; one common-prefix length serves all orders).  Words get the index of their first equal
+ * occurrence across both sides and are counted over those ids.  256 threads for Hmax <= S2T_CHRF_GROUP_LEN tokens, 1,024 above
+ * (the character count is not known to the host; inside, a wave without positions skips the loops).
+ * Limits: S2T_CHRF_MAX_LEN tokens of padded width (the width of s2t_bleu_pairs: lists of hypotheses) and S2T_CHRF_MAX_CHARS
+ * characters per side (at four bytes per code point both sides take 32.8 KB of LDS, with the words' starts and ids 65.6 KB of the
+ * CU's 160 KB: two workgroups per CU with words, four without).
+ * Refusals, before anything is launched: S2T_OK at once for P <= 0; S2T_EINVAL for a NULL required pointer (hyp, hyp_len, ref,
+ * ref_len, pieces, piece_off, stats, status), a negative width, V or n_pieces, an element size other than 4 or 8, a side without a
+ * map whose rows are not P (with one: negative), unk >= V, char_order outside [1, S2T_CHRF_MAX_CHAR_ORDER] or word_order outside
+ * [0, S2T_CHRF_MAX_WORD_ORDER]; S2T_ENOTSUP for a width above S2T_CHRF_MAX_LEN. */
+#define S2T_CHRF_MAX_LEN 1024
+#define S2T_CHRF_MAX_CHARS 4095
+#define S2T_CHRF_GROUP_LEN 64
+#define S2T_CHRF_MAX_CHAR_ORDER 6
+#define S2T_CHRF_MAX_WORD_ORDER 2
+#define S2T_CHRF_SEP 0xffffffffu
+int s2t_chrf_stats(const void* hyp, const void* hyp_len, int hyp_elem, const void* ref, const void* ref_len, int ref_elem,
+                   const int* hyp_row, const int* ref_row, int P, int Hmax, int Rmax, int Hrows, int Rrows,
+                   const unsigned int* pieces, const int* piece_off, int n_pieces, int V, long long unk, int char_order,
+                   int word_order, int* stats, int* status, void* stream);
 /* ---- Kaldi log-mel filterbanks of waveforms (csrc/fbank.hip): torchaudio.compliance.kaldi.fbank with its defaults, restated.
  * Frames: W samples long, S apart, N the next power of two >= W.  An utterance of n samples has m = 0 frames if n < W, else
  * m = 1 + (n - W) / S (snip-edges); frame t is the samples [t*S, t*S + W).  No sample at or behind n is read into a result.
