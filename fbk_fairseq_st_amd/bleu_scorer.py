@@ -15,10 +15,10 @@ import math
 import torch
 
 from . import kernels as K
+from .token_rows import as_ints, best_rows, nbest_tables, pad_rows
 
 MAX_LEN = K.BLEU_MAX_LEN                # S2T_BLEU_MAX_LEN
 STATUS = {0: "done", 2: "refused: a length outside the padded width, or a reference row outside the references"}
-_INTS = (torch.int32, torch.int64)
 _SUMS = ("ref_len", "sys_len", "match1", "count1", "match2", "count2", "match3", "count3", "match4", "count4")
 
 
@@ -54,10 +54,10 @@ class BleuScorer:
         returns; the best hypothesis of every sentence is scored (a sentence without one counts as empty).  Returns what `score`
         returns."""
         dev = ref.device
-        best = [h[0]["tokens"].to(dev).reshape(-1) if len(h) else torch.empty((0,), dtype=torch.int64, device=dev) for h in hypos]
+        best = best_rows(hypos, dev)
         if len(best) != ref.shape[0]:
             raise ValueError("BleuScorer.score_hypotheses: %d sentences of hypotheses, %d references" % (len(best), ref.shape[0]))
-        hyp, hyp_len = _pad_rows(best, dev)
+        hyp, hyp_len = pad_rows(best, dev)
         return self.score(hyp, hyp_len, ref, ref_len)
 
     @torch.no_grad()
@@ -74,37 +74,13 @@ class BleuScorer:
         B = len(hypos)
         if B != ref.shape[0]:
             raise ValueError("BleuScorer.score_nbest: %d sentences of hypotheses, %d references" % (B, ref.shape[0]))
-        counts = [len(h) for h in hypos]
-        N = max(counts + [1])
-        flat = [h["tokens"].to(dev).reshape(-1) for hs in hypos for h in hs]
-        sent = [b for b, n in enumerate(counts) for _ in range(n)]             # lists' shapes: no host read
-        slot = [k for n in counts for k in range(n)]
-        hyp, hyp_len = _pad_rows(flat, dev)
-        rows = torch.tensor(sent, dtype=torch.int32, device=dev)
-        got = self._run(hyp, hyp_len, ref, ref_len, rows)
-        at = (rows.long(), torch.tensor(slot, dtype=torch.int64, device=dev))
-        stats = torch.zeros((B, N, 10), dtype=torch.int32, device=dev)
-        status = torch.zeros((B, N), dtype=torch.int32, device=dev)
-        bleu = torch.full((B, N), -1.0, dtype=torch.float64, device=dev)
-        stats[at], status[at], bleu[at] = got["stats"], got["status"], got["sentence_bleu"]
-        # the first index of the row's maximum
-        cols = torch.arange(N, device=dev).expand(B, N)
-        oracle = torch.where(bleu == bleu.max(1, keepdim=True).values, cols, torch.full_like(cols, N)).min(1).values if B else \
-            torch.zeros((0,), dtype=torch.int64, device=dev)
+        stats, status, bleu, n_hyp, oracle, pick = nbest_tables(
+            hypos, B, dev, lambda hyp, hyp_len, rows: self._run(hyp, hyp_len, ref, ref_len, rows), 10, "sentence_bleu")
         out = _fields(stats, status, bleu)
-        out["n_hyp"] = torch.tensor(counts, dtype=torch.int64, device=dev)
-        out["oracle"] = oracle
+        out["n_hyp"], out["oracle"] = n_hyp, oracle
         if accumulate is not None and B:
-            pick = oracle if accumulate == "oracle" else torch.zeros_like(oracle)
-            self._add(stats.gather(1, pick[:, None, None].expand(B, 1, 10)).sum((0, 1), dtype=torch.int64))
+            self._add(pick(accumulate))
         return out
-
-    @staticmethod
-    def _ints(tok, ln, dev):
-        tok = tok.to(dev)
-        if tok.dtype not in _INTS:
-            tok = tok.long()
-        return tok, ln.to(device=dev, dtype=tok.dtype)
 
     def _run(self, hyp, hyp_len, ref, ref_len, rows):
         if hyp.dim() != 2 or ref.dim() != 2 or (rows is None and hyp.shape[0] != ref.shape[0]):
@@ -114,8 +90,8 @@ class BleuScorer:
             raise ValueError("BleuScorer: padded widths of at most %d tokens (S2T_BLEU_MAX_LEN), got %d and %d"
                              % (MAX_LEN, hyp.shape[1], ref.shape[1]))
         dev = hyp.device
-        hyp, hyp_len = self._ints(hyp, hyp_len, dev)
-        ref, ref_len = self._ints(ref, ref_len, dev)
+        hyp, hyp_len = as_ints(hyp, hyp_len, dev)
+        ref, ref_len = as_ints(ref, ref_len, dev)
         stats, status = K.bleu_stats(hyp, hyp_len, ref, ref_len, self.pad, self.eos, self.unk, ref_row=rows)
         return _fields(stats, status, sentence_bleu(stats))
 
@@ -179,14 +155,3 @@ def sentence_bleu(stats):
 def _fields(stats, status, bleu):
     return {"stats": stats, "match": stats[..., 2::2], "count": stats[..., 3::2], "sys_len": stats[..., 1], "ref_len": stats[..., 0],
             "status": status, "sentence_bleu": bleu}
-
-
-def _pad_rows(rows, dev):
-    """1-D token tensors -> (matrix padded with zeros, lengths); the lengths come from shapes: no host read"""
-    dtype = torch.int32 if rows and all(t.dtype == torch.int32 for t in rows) else torch.int64
-    lens = [t.numel() for t in rows]
-    width = max(lens + [0])
-    mat = torch.zeros((len(rows), width), dtype=dtype, device=dev)
-    if width:
-        mat = torch.nn.utils.rnn.pad_sequence([t.to(dtype) for t in rows], batch_first=True)
-    return mat, torch.tensor(lens, dtype=dtype, device=dev)

@@ -18,14 +18,13 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .bleu_scorer import _pad_rows
+from .token_rows import as_ints, best_rows, nbest_tables, pad_rows
 
 MAX_LEN = K.CHRF_MAX_LEN                # S2T_CHRF_MAX_LEN
 MAX_CHARS = K.CHRF_MAX_CHARS            # S2T_CHRF_MAX_CHARS
 SEP = K.CHRF_SEP                        # S2T_CHRF_SEP
 STATUS = {0: "done", 2: "refused: a row outside its matrix, a length outside the padded width, a token outside the dictionary, or "
                         "a side of more than %d characters" % MAX_CHARS}
-_INTS = (torch.int32, torch.int64)
 _ORDERS = 8                             # six character orders, two word orders
 _SUMS = tuple("%s%d_%s" % (kind, n, what) for kind, top in (("char", 6), ("word", 2)) for n in range(1, top + 1)
               for what in ("hyp", "ref", "match"))
@@ -121,10 +120,10 @@ class ChrfScorer:
         """hypos: per sentence a list of dicts with `tokens` (1-D device tensors), best first; the best hypothesis of every sentence
         is scored (a sentence without one counts as empty).  Returns what `score` returns."""
         dev = ref.device
-        best = [h[0]["tokens"].to(dev).reshape(-1) if len(h) else torch.empty((0,), dtype=torch.int64, device=dev) for h in hypos]
+        best = best_rows(hypos, dev)
         if len(best) != ref.shape[0]:
             raise ValueError("ChrfScorer.score_hypotheses: %d sentences of hypotheses, %d references" % (len(best), ref.shape[0]))
-        hyp, hyp_len = _pad_rows(best, dev)
+        hyp, hyp_len = pad_rows(best, dev)
         return self.score(hyp, hyp_len, ref, ref_len)
 
     @torch.no_grad()
@@ -140,28 +139,11 @@ class ChrfScorer:
         B = len(hypos)
         if B != ref.shape[0]:
             raise ValueError("ChrfScorer.score_nbest: %d sentences of hypotheses, %d references" % (B, ref.shape[0]))
-        counts = [len(h) for h in hypos]
-        N = max(counts + [1])
-        flat = [h["tokens"].to(dev).reshape(-1) for hs in hypos for h in hs]
-        sent = [b for b, n in enumerate(counts) for _ in range(n)]             # lists' shapes: no host read
-        slot = [k for n in counts for k in range(n)]
-        hyp, hyp_len = _pad_rows(flat, dev)
-        rows = torch.tensor(sent, dtype=torch.int32, device=dev)
-        got = self._run(hyp, hyp_len, None, ref, ref_len, rows)
-        at = (rows.long(), torch.tensor(slot, dtype=torch.int64, device=dev))
-        stats = torch.zeros((B, N, K.CHRF_STATS), dtype=torch.int32, device=dev)
-        status = torch.zeros((B, N), dtype=torch.int32, device=dev)
-        chrf = torch.full((B, N), -1.0, dtype=torch.float64, device=dev)
-        stats[at], status[at], chrf[at] = got["stats"], got["status"], got["sentence_chrf"]
-        cols = torch.arange(N, device=dev).expand(B, N)                        # the first index of the row's maximum
-        oracle = torch.where(chrf == chrf.max(1, keepdim=True).values, cols, torch.full_like(cols, N)).min(1).values if B else \
-            torch.zeros((0,), dtype=torch.int64, device=dev)
-        out = {"stats": stats, "status": status, "sentence_chrf": chrf, "n_hyp": torch.tensor(counts, dtype=torch.int64, device=dev),
-               "oracle": oracle}
+        stats, status, chrf, n_hyp, oracle, pick = nbest_tables(
+            hypos, B, dev, lambda hyp, hyp_len, rows: self._run(hyp, hyp_len, None, ref, ref_len, rows), K.CHRF_STATS, "sentence_chrf")
         if accumulate is not None and B:
-            pick = oracle if accumulate == "oracle" else torch.zeros_like(oracle)
-            self._add(stats.gather(1, pick[:, None, None].expand(B, 1, K.CHRF_STATS)).sum((0, 1), dtype=torch.int64))
-        return out
+            self._add(pick(accumulate))
+        return {"stats": stats, "status": status, "sentence_chrf": chrf, "n_hyp": n_hyp, "oracle": oracle}
 
     @torch.no_grad()
     def score_pairs(self, hyp, hyp_len, hyp_row, ref, ref_len, ref_row):
@@ -174,21 +156,14 @@ class ChrfScorer:
         self._add(out["stats"].sum(0, dtype=torch.int64))
         return out
 
-    @staticmethod
-    def _ints(tok, ln, dev):
-        tok = tok.to(dev)
-        if tok.dtype not in _INTS:
-            tok = tok.long()
-        return tok, ln.to(device=dev, dtype=tok.dtype)
-
     def _run(self, hyp, hyp_len, hyp_row, ref, ref_len, ref_row):
         if hyp.shape[1] > MAX_LEN or ref.shape[1] > MAX_LEN:
             raise ValueError("ChrfScorer: padded widths of at most %d tokens (S2T_CHRF_MAX_LEN), got %d and %d"
                              % (MAX_LEN, hyp.shape[1], ref.shape[1]))
         dev = hyp.device
         same = ref is hyp
-        hyp, hyp_len = self._ints(hyp, hyp_len, dev)
-        ref, ref_len = (hyp, hyp_len) if same else self._ints(ref, ref_len, dev)
+        hyp, hyp_len = as_ints(hyp, hyp_len, dev)
+        ref, ref_len = (hyp, hyp_len) if same else as_ints(ref, ref_len, dev)
         hyp_row = None if hyp_row is None else hyp_row.to(device=dev, dtype=torch.int32)
         ref_row = None if ref_row is None else ref_row.to(device=dev, dtype=torch.int32)
         pieces, off = self.table_on(dev)

@@ -5,27 +5,26 @@
 // wave per SIMD at 16 x 64 hypotheses of 60 tokens, and a wave's loop waits for its LDS broadcast every step; the slice costs the
 // candidate's half of the work once more per slice (measured: DESIGN.md 5i).
 //   * What bleu_stats.hip does per pair is split here into the half that depends on the candidate only and the half that depends on
-//     the pair.  Candidate position i matches pseudo-reference r at order n iff rank_n(i) < cref_n(i, r): rank_n counts the earlier
-//     candidate positions that hold the n-gram of position i, cref_n the positions of r that hold it.  The candidate is staged and
-//     trimmed once per workgroup and every thread takes its four ranks once (the k < i loop of bleu_stats.hip); they stay in
-//     registers while the workgroup walks its slice.
+//     the pair (ngram_match.hpp states the rule and holds the loops both files run): rank_n(i) needs the candidate alone,
+//     cref_n(i, r) the pseudo-reference r.  The candidate is staged and trimmed once per workgroup and every thread takes its four
+//     ranks once (BLEU_RANK); they stay in registers while the workgroup walks its slice.
 //   * Staging: rows are copied to LDS as they lie in memory (a chunk of pseudo-references is one span of the matrix, copied in whole
 //     padded rows: no load waits for a length or for another load); the trim is taken afterwards, in LDS, as a first index and a
 //     length (a scan from both ends that usually ends after a step or two), so nothing is moved and no ballot is needed.
-//     Windows may read up to three tokens behind a trimmed row: those are inside the row's four slack slots and are cut -- by
-//     `clip` on the candidate's side, by the tail of the j loop on the pseudo-reference's -- so they may hold anything.
+//     Windows may read up to three tokens behind a trimmed row: those are inside the row's four slack slots, which are not
+//     zeroed here (ngram_match.hpp: they may hold anything).
 //   * The slice is walked in chunks of S2T_MBR_CHUNK pseudo-references (the header's switch: as many padded rows as
 //     S2T_MBR_CHUNK_BYTES hold, at most the slice).  Per chunk: every thread copies its share of the chunk's rows; barrier;
 //     lane g of every wave trims row g (each wave for itself: the lengths come out of a lane by v_readlane, nothing is exchanged);
-//     every wave that holds candidate positions runs the j loop of bleu_stats.hip over each row, with wave-uniform bounds and LDS
-//     broadcasts, and turns its lanes' four match bits into counts by ballots.  One wave (Hmax <= 64) writes the ten numbers from
-//     there.  Several waves leave their counts in LDS; behind a second barrier thread g sums row g's and writes its ten numbers
-//     while the others already copy the next chunk, if there is one: the rows are free once every wave is past that barrier, and
-//     the counts are read before their reader arrives at the next chunk's first barrier.
+//     every wave that holds candidate positions runs BLEU_CREF, the j loop of bleu_stats.hip, over each row, with wave-uniform
+//     bounds and LDS broadcasts, and turns its lanes' four match bits into counts by ballots.  One wave (Hmax <= 64) writes the ten
+//     numbers from there.  Several waves leave their counts in LDS; behind a second barrier thread g sums row g's and writes its
+//     ten numbers while the others already copy the next chunk, if there is one: the rows are free once every wave is past that
+//     barrier, and the counts are read before their reader arrives at the next chunk's first barrier.
 //   * A candidate `unk` cuts the window of its position (`clip`), as in bleu_stats.hip: an n-gram with an unk can only equal one
 //     with an unk on the reference side, which never matches.
 //   * Tokens are staged as 32-bit when both sides are int32 and as 64-bit otherwise.
-#include "common.hpp"
+#include "ngram_match.hpp"
 #include "s2t_hip.h"
 
 #ifndef MBR_SLICE                                                   // a measurement twin is built with another (tools/mbr_time.py)
@@ -43,10 +42,6 @@ struct PairArgs {
 };
 
 constexpr int MBR_SLACK = 4;                                        // slots behind a staged row: windows may read three of them
-
-__device__ __forceinline__ long long pair_tok(const void* p, int es, size_t i) {
-    return es == 4 ? (long long)reinterpret_cast<const int*>(p)[i] : reinterpret_cast<const long long*>(p)[i];
-}
 
 // the trim of a staged row of `len` tokens: the first index that is not pad and the length up to the last token that is neither eos
 // nor pad, never less than 1; 0 for a row of pads
@@ -71,7 +66,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
     int* st = p.status + (size_t)c * M;
 
     // ---- the candidate's list; what is refused (the same in every thread of the workgroup)
-    const long long hq = pair_tok(p.cand_len, p.cand_elem, c);
+    const long long hq = int_at(p.cand_len, p.cand_elem, c);
     const int sent = p.cand_sent[c];
     int lo = 0, n = -1;                                             // n: the list's length, -1 for a row without a list
     if (sent >= 0 && sent < p.B) {
@@ -100,7 +95,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
     T* rs = hs + hstride;
     {
         const char* hrow = reinterpret_cast<const char*>(p.cand) + (size_t)c * p.Hmax * p.cand_elem;
-        for (int t = tid; t < (int)hq; t += NT) hs[t] = (T)pair_tok(hrow, p.cand_elem, t);
+        for (int t = tid; t < (int)hq; t += NT) hs[t] = (T)int_at(hrow, p.cand_elem, t);
     }
     __syncthreads();
     int hf, H;
@@ -119,35 +114,8 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
         const int u = (long long)h0 == p.unk ? 0 : (long long)h1 == p.unk ? 1 : (long long)h2 == p.unk ? 2 : (long long)h3 == p.unk ? 3 : 4;
         clip = min(clip, u);
     }
-    // lim: the tokens window x has (uniform); ok: this lane takes part
-#define PAIR_TALLY(n1, n2, n3, n4, lim, ok)                         \
-    {                                                               \
-        int a = (int)(h0 == x0) & (int)(ok);                        \
-        n1 += a;                                                    \
-        a &= (int)(h1 == x1) & (int)((lim) >= 2);                   \
-        n2 += a;                                                    \
-        a &= (int)(h2 == x2) & (int)((lim) >= 3);                   \
-        n3 += a;                                                    \
-        a &= (int)(h3 == x3) & (int)((lim) >= 4);                   \
-        n4 += a;                                                    \
-    }
     int r1 = 0, r2 = 0, r3 = 0, r4 = 0;
-    if (q0 < H) {   // candidate positions k < i.  k <= H - 2, so the reads stay inside the slack slots
-        T x0 = ht[0], x1 = ht[1], x2 = ht[2];
-        const int kend = min(q0 + 63, H - 1);
-#pragma clang loop vectorize(disable) unroll_count(4)
-        for (int k = 0; k < q0; ++k) {                              // in front of every position of this wave
-            const T x3 = ht[k + 3];
-            PAIR_TALLY(r1, r2, r3, r4, 4, true)
-            x0 = x1; x1 = x2; x2 = x3;
-        }
-#pragma clang loop vectorize(disable) unroll_count(4)
-        for (int k = q0; k < kend; ++k) {
-            const T x3 = ht[k + 3];
-            PAIR_TALLY(r1, r2, r3, r4, 4, k < i)
-            x0 = x1; x1 = x2; x2 = x3;
-        }
-    }
+    if (q0 < H) BLEU_RANK(ht, H, q0, i, r1, r2, r3, r4)             // candidate positions k < i, once for the whole list
 
     // ---- the list, a chunk at a time
     for (int g0 = k0; g0 < gend; g0 += p.chunk) {                   // uniform
@@ -159,7 +127,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
 #pragma clang loop unroll_count(8)
             for (int e = tid; e < total; e += NT) {
                 const int g = e / p.Pmax;
-                rs[e + g * MBR_SLACK] = (T)pair_tok(span, p.ref_elem, e);
+                rs[e + g * MBR_SLACK] = (T)int_at(span, p.ref_elem, e);
             }
         }
         __syncthreads();
@@ -167,7 +135,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
         int rf = 0, R = 0;
         bool rbad = false;
         if (lane < G) {
-            const long long rq = pair_tok(p.ref_len, p.ref_elem, (size_t)(lo + g0 + lane));
+            const long long rq = int_at(p.ref_len, p.ref_elem, (size_t)(lo + g0 + lane));
             rbad = rq < 0 || rq > p.Pmax;
             if (!rbad) pair_trim(rs + lane * rstride, (int)rq, p.pad, p.eos, rf, R);
         }
@@ -177,20 +145,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
             if (q0 < H) {
                 const T* rt = rs + g * rstride + __builtin_amdgcn_readlane(rf, g);
                 int c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-                T x0 = rt[0], x1 = rt[1], x2 = rt[2];
-                const int full = max(Rg - 3, 0);
-#pragma clang loop vectorize(disable) unroll_count(4)
-                for (int j = 0; j < full; ++j) {
-                    const T x3 = rt[j + 3];
-                    PAIR_TALLY(c1, c2, c3, c4, 4, true)
-                    x0 = x1; x1 = x2; x2 = x3;
-                }
-#pragma clang loop vectorize(disable) unroll(disable)
-                for (int j = full; j < Rg; ++j) {                   // the last windows: cut by the pseudo-reference's end
-                    const T x3 = rt[j + 3];
-                    PAIR_TALLY(c1, c2, c3, c4, Rg - j, true)
-                    x0 = x1; x1 = x2; x2 = x3;
-                }
+                BLEU_CREF(rt, Rg, c1, c2, c3, c4)
                 m12 = (uint32_t)__popcll(__ballot(clip >= 1 && r1 < c1)) | ((uint32_t)__popcll(__ballot(clip >= 2 && r2 < c2)) << 16);
                 m34 = (uint32_t)__popcll(__ballot(clip >= 3 && r3 < c3)) | ((uint32_t)__popcll(__ballot(clip >= 4 && r4 < c4)) << 16);
             }
@@ -198,7 +153,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
                 if (lane == 0) { s_part[g][wave][0] = m12; s_part[g][wave][1] = m34; }
             } else {
                 const bool bad = __builtin_amdgcn_readlane((int)rbad, g) != 0;
-                // lane 0 reflen, lane 1 predlen; lanes 2 n and 2 n + 1 match_n and count_n
+                // bleu_record's ten numbers, one per lane: lane 0 reflen, lane 1 predlen; lanes 2 n and 2 n + 1 match_n and count_n
                 const int ord = lane >> 1;
                 const int v = lane & 1 ? (lane == 1 ? H : max(H - ord + 1, 0))
                                        : lane == 0 ? Rg : ord == 1 ? (int)(m12 & 0xffff) : ord == 2 ? (int)(m12 >> 16) : ord == 3 ? (int)(m34 & 0xffff) : (int)(m34 >> 16);
@@ -218,17 +173,12 @@ __global__ __launch_bounds__(64 * NW) void bleu_pairs_kernel(const PairArgs p) {
 #pragma unroll
                     for (int q = 0; q < 10; ++q) o[q] = 0;
                 } else {
-                    o[0] = R; o[1] = H;
-                    o[2] = (int)(m12 & 0xffff); o[3] = H;
-                    o[4] = (int)(m12 >> 16);    o[5] = max(H - 1, 0);
-                    o[6] = (int)(m34 & 0xffff); o[7] = max(H - 2, 0);
-                    o[8] = (int)(m34 >> 16);    o[9] = max(H - 3, 0);
+                    bleu_record(o, R, H, m12, m34);
                 }
                 st[g0 + tid] = rbad ? 2 : 0;
             }
         }
     }
-#undef PAIR_TALLY
 }
 
 template <typename T, int NW>

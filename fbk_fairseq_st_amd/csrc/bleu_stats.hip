@@ -4,21 +4,16 @@
 // One launch, one sentence per workgroup, no atomics, no host read.
 //   * Prologue: both sides are trimmed inside their lengths (ballots give the first non-pad token and the last token that is
 //     neither eos nor pad) and the trimmed tokens are staged in LDS, four zeroed slots behind each side.
-//   * Position-wise matching: hypothesis position i matches at order n iff rank_n(i) < cref_n(i), where rank_n counts the earlier
-//     hypothesis positions and cref_n the reference positions that hold the same n-gram.  A lane owns position i with hyp[i .. i+3]
-//     in registers and walks all reference positions j, then all hypothesis positions k < i, with wave-uniform loops: every lane
-//     reads the same window x[j .. j+3] (LDS broadcasts, one new token per step).  The common prefix of the two windows serves the
-//     four orders at once: a pair is an order-n hit for every n up to its length.
+//   * Position-wise matching, the loops of ngram_match.hpp (which states the rule and why the windows may read the slack slots): a
+//     lane owns position i with hyp[i .. i+3] in registers and takes cref over all reference positions (BLEU_CREF), then rank over
+//     the hypothesis positions in front of it (BLEU_RANK).
 //   * Clipping: the window of position i is cut at the hypothesis' end and at its first `unk` (an n-gram with an unk in the
-//     hypothesis can only equal one with an unk in the reference, which never matches); that cut is applied once, after the loops,
-//     so what the lanes read beyond it may be anything.  The reference's end cuts the last three windows of the j loop, which is
-//     uniform and runs as a tail of its own.  In the k loop nothing is cut: k < i keeps window k inside the sentence wherever window
-//     i is.
+//     hypothesis can only equal one with an unk in the reference, which never matches); that cut is applied once, after the loops.
 //   * Wave form (Hmax <= 64): one wave, lane = position.  Workgroup form: 256 threads up to Hmax = 256, 1,024 threads above (thread
 //     t owns the positions t + 1,024 q); the waves never meet between the staging barrier and the final sum.  A wave's loop waits
 //     for its LDS broadcast every step, so a long hypothesis wants several waves on each of the CU's four SIMDs.
 //   * Tokens are staged as 32-bit when both sides are int32 and as 64-bit otherwise (dynamic LDS, up to 2 x 4,099 x 8 bytes).
-#include "common.hpp"
+#include "ngram_match.hpp"
 #include "s2t_hip.h"
 
 namespace {
@@ -33,10 +28,6 @@ struct BleuArgs {
 
 constexpr int BLEU_SLACK = 4;                                       // zeroed slots behind a staged side: windows may read them
 
-__device__ __forceinline__ long long bleu_tok(const void* p, int es, long i) {
-    return es == 4 ? (long long)reinterpret_cast<const int*>(p)[i] : reinterpret_cast<const long long*>(p)[i];
-}
-
 // what one wave sees of a side: the first index that is not pad (len if none) and the last that is neither eos nor pad (-1 if none)
 template <int NW>
 __device__ __forceinline__ void bleu_scan(const char* row, int es, int len, long long pad, long long eos, int& first, int& last) {
@@ -44,7 +35,7 @@ __device__ __forceinline__ void bleu_scan(const char* row, int es, int len, long
     first = len; last = -1;
     for (int t0 = 0; t0 < len; t0 += 64 * NW) {
         const int t = t0 + tid;
-        const long long x = t < len ? bleu_tok(row, es, t) : pad;
+        const long long x = t < len ? int_at(row, es, t) : pad;
         const unsigned long long np = __ballot(t < len && x != pad);
         const unsigned long long kp = __ballot(t < len && x != pad && x != eos);
         const int base = t0 + 64 * wave;
@@ -61,10 +52,10 @@ __global__ __launch_bounds__(64 * NW) void bleu_stats_kernel(const BleuArgs p) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int* out = p.stats + (size_t)b * 10;
 
-    const long long hq = bleu_tok(p.hyp_len, p.hyp_elem, b);
+    const long long hq = int_at(p.hyp_len, p.hyp_elem, b);
     const long long rowq = p.ref_row ? (long long)p.ref_row[b] : (long long)b;
     bool refused = hq < 0 || hq > p.Hmax || rowq < 0 || rowq >= p.Rrows;
-    const long long rq = refused ? 0 : bleu_tok(p.ref_len, p.ref_elem, rowq);
+    const long long rq = refused ? 0 : int_at(p.ref_len, p.ref_elem, rowq);
     refused = refused || rq < 0 || rq > p.Rmax;
     if (refused) {                                                  // the same in every thread of the workgroup
         if (tid < 10) out[tid] = 0;
@@ -95,8 +86,8 @@ __global__ __launch_bounds__(64 * NW) void bleu_stats_kernel(const BleuArgs p) {
     // ---- stage the trimmed tokens
     T* hs = reinterpret_cast<T*>(bleu_smem);
     T* rs = hs + p.Hmax + BLEU_SLACK;
-    for (int t = tid; t < H + BLEU_SLACK; t += NT) hs[t] = t < H ? (T)bleu_tok(hrow, p.hyp_elem, hf + t) : (T)0;
-    for (int t = tid; t < R + BLEU_SLACK; t += NT) rs[t] = t < R ? (T)bleu_tok(rrow, p.ref_elem, rf + t) : (T)0;
+    for (int t = tid; t < H + BLEU_SLACK; t += NT) hs[t] = t < H ? (T)int_at(hrow, p.hyp_elem, hf + t) : (T)0;
+    for (int t = tid; t < R + BLEU_SLACK; t += NT) rs[t] = t < R ? (T)int_at(rrow, p.ref_elem, rf + t) : (T)0;
     __syncthreads();
 
     // ---- matches
@@ -113,51 +104,8 @@ __global__ __launch_bounds__(64 * NW) void bleu_stats_kernel(const BleuArgs p) {
             clip = min(clip, u);
         }
         int c1 = 0, c2 = 0, c3 = 0, c4 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0;
-        // lim: the tokens window x has (uniform); ok: this lane takes part
-#define BLEU_TALLY(n1, n2, n3, n4, lim, ok)                         \
-        {                                                           \
-            int a = (int)(h0 == x0) & (int)(ok);                    \
-            n1 += a;                                                \
-            a &= (int)(h1 == x1) & (int)((lim) >= 2);               \
-            n2 += a;                                                \
-            a &= (int)(h2 == x2) & (int)((lim) >= 3);               \
-            n3 += a;                                                \
-            a &= (int)(h3 == x3) & (int)((lim) >= 4);               \
-            n4 += a;                                                \
-        }
-        {   // reference positions j: cref
-            T x0 = rs[0], x1 = rs[1], x2 = rs[2];
-            const int full = max(R - 3, 0);
-#pragma clang loop vectorize(disable) unroll_count(4)
-            for (int j = 0; j < full; ++j) {
-                const T x3 = rs[j + 3];
-                BLEU_TALLY(c1, c2, c3, c4, 4, true)
-                x0 = x1; x1 = x2; x2 = x3;
-            }
-#pragma clang loop vectorize(disable) unroll(disable)
-            for (int j = full; j < R; ++j) {                        // the last windows: cut by the reference's end
-                const T x3 = rs[j + 3];
-                BLEU_TALLY(c1, c2, c3, c4, R - j, true)
-                x0 = x1; x1 = x2; x2 = x3;
-            }
-        }
-        {   // hypothesis positions k < i: rank.  k <= H - 2, so the reads stay inside the zeroed slots
-            T x0 = hs[0], x1 = hs[1], x2 = hs[2];
-            const int kend = min(q0 + 63, H - 1);
-#pragma clang loop vectorize(disable) unroll_count(4)
-            for (int k = 0; k < q0; ++k) {                          // in front of every position of this wave
-                const T x3 = hs[k + 3];
-                BLEU_TALLY(r1, r2, r3, r4, 4, true)
-                x0 = x1; x1 = x2; x2 = x3;
-            }
-#pragma clang loop vectorize(disable) unroll_count(4)
-            for (int k = q0; k < kend; ++k) {
-                const T x3 = hs[k + 3];
-                BLEU_TALLY(r1, r2, r3, r4, 4, k < i)
-                x0 = x1; x1 = x2; x2 = x3;
-            }
-        }
-#undef BLEU_TALLY
+        BLEU_CREF(rs, R, c1, c2, c3, c4)                            // reference positions j
+        BLEU_RANK(hs, H, q0, i, r1, r2, r3, r4)                     // hypothesis positions k < i
         m12 += (uint32_t)(clip >= 1 && r1 < c1) + ((uint32_t)(clip >= 2 && r2 < c2) << 16);
         m34 += (uint32_t)(clip >= 3 && r3 < c3) + ((uint32_t)(clip >= 4 && r4 < c4) << 16);
     }
@@ -173,11 +121,7 @@ __global__ __launch_bounds__(64 * NW) void bleu_stats_kernel(const BleuArgs p) {
         for (int w = 0; w < NW; ++w) { m12 += (uint32_t)s_red[w][0]; m34 += (uint32_t)s_red[w][1]; }
     }
     if (tid == 0) {
-        out[0] = R; out[1] = H;
-        out[2] = (int)(m12 & 0xffff); out[3] = H;
-        out[4] = (int)(m12 >> 16);    out[5] = max(H - 1, 0);
-        out[6] = (int)(m34 & 0xffff); out[7] = max(H - 2, 0);
-        out[8] = (int)(m34 >> 16);    out[9] = max(H - 3, 0);
+        bleu_record(out, R, H, m12, m34);
         p.status[b] = 0;
     }
 }

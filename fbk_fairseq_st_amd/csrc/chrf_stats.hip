@@ -10,11 +10,11 @@
 //     written behind a barrier.  A second scan lists the word starts, the marks are wiped, and every word gets the index of its
 //     first equal occurrence in the list "hypothesis words, then reference words" (lengths and code points compared: no hash), so
 //     word n-grams are n-grams of 16-bit ids.
-//   * Matches, for characters and for word ids alike: the position-wise counting of bleu_stats.hip.  Position i matches at order n
-//     iff rank_n(i) < cref_n(i), the earlier hypothesis positions and the reference positions that hold the same n-gram.  A lane
-//     owns position i with its window in registers and walks the other positions with wave-uniform loops (LDS broadcasts, one new
-//     element per step); the common prefix of two windows serves all orders at once.  The hypothesis' end cuts the orders of a
-//     position once, after the loops; the reference's end cuts the last windows of its loop, which run as a tail of their own.
+//   * Matches, for characters (N = 6 on 32-bit code points) and for word ids (N = 2 on 16-bit ids) alike: the position-wise
+//     counting that ngram_match.hpp states (the rule, why the windows may read the slack slots), in loops of its own for N orders,
+//     chrf_matches: on functions shared with the BLEU kernels this kernel was 15 to 35 % slower at 60-token rows
+//     (profiles/ngram_match_ab.txt, section 2).  tests/test_ngram_match_gpu.py holds its numbers to bleu_stats.hip's.  The
+//     hypothesis' end cuts the orders of a position once, after the loops.
 //   * Threads: 256 for hypotheses up to S2T_CHRF_GROUP_LEN tokens wide, 1,024 above (the width is what the host knows without a
 //     read).  Inside, wave w takes the positions 64 w + lane (+ threads, ...): a wave without positions skips the loops, so the
 //     work follows the character count in steps of 64.
@@ -39,10 +39,6 @@ constexpr int CHRF_CAP = S2T_CHRF_MAX_CHARS + CHRF_SLACK;           // 4,104 ele
 constexpr uint32_t CHRF_START = 0x80000000u;                        // mark: this character begins a word
 constexpr uint32_t CHRF_CODE = 0x001fffffu;
 constexpr int CHRF_OVER = S2T_CHRF_MAX_CHARS + 1;                   // a thread's count saturates here: the side is refused anyway
-
-__device__ __forceinline__ long long chrf_tok(const void* p, int es, long i) {
-    return es == 4 ? (long long)reinterpret_cast<const int*>(p)[i] : reinterpret_cast<const long long*>(p)[i];
-}
 
 // the piece of a token: [a, b) of pieces; false for a token outside [0, V) or offsets that are no range of the table
 __device__ __forceinline__ bool chrf_piece(const ChrfArgs& p, long long tok, bool ref_side, int& a, int& b) {
@@ -92,7 +88,7 @@ __device__ __forceinline__ void chrf_measure(const ChrfArgs& p, const char* row,
     n = 0; bad = 0; flag = 0;
     for (int t = t0; t < t1; ++t) {
         int a, b;
-        if (!chrf_piece(p, chrf_tok(row, es, t), ref_side, a, b)) { ++bad; continue; }
+        if (!chrf_piece(p, int_at(row, es, t), ref_side, a, b)) { ++bad; continue; }
         for (int j = a; j < b && n < CHRF_OVER; ++j) {
             const bool sep = p.pieces[j] == S2T_CHRF_SEP;
             n += sep ? 0 : 1;
@@ -109,7 +105,7 @@ __device__ __forceinline__ void chrf_expand(const ChrfArgs& p, const char* row, 
     bool brk = flag != 1;
     for (int t = t0; t < t1; ++t) {
         int a, b;
-        if (!chrf_piece(p, chrf_tok(row, es, t), ref_side, a, b)) continue;        // cannot happen: such a pair was refused
+        if (!chrf_piece(p, int_at(row, es, t), ref_side, a, b)) continue;        // cannot happen: such a pair was refused
         for (int j = a; j < b; ++j) {
             const uint32_t c = p.pieces[j];
             if (c == S2T_CHRF_SEP) { brk = true; continue; }
@@ -227,8 +223,8 @@ __global__ __launch_bounds__(64 * NW) void chrf_stats_kernel(const ChrfArgs p) {
     const long long hrow_i = p.hyp_row ? (long long)p.hyp_row[b] : (long long)b;
     const long long rrow_i = p.ref_row ? (long long)p.ref_row[b] : (long long)b;
     bool refused = hrow_i < 0 || hrow_i >= p.Hrows || rrow_i < 0 || rrow_i >= p.Rrows;
-    const long long hq = refused ? 0 : chrf_tok(p.hyp_len, p.hyp_elem, hrow_i);
-    const long long rq = refused ? 0 : chrf_tok(p.ref_len, p.ref_elem, rrow_i);
+    const long long hq = refused ? 0 : int_at(p.hyp_len, p.hyp_elem, hrow_i);
+    const long long rq = refused ? 0 : int_at(p.ref_len, p.ref_elem, rrow_i);
     refused = refused || hq < 0 || hq > p.Hmax || rq < 0 || rq > p.Rmax;
     int H = 0, R = 0, hat = 0, hflag = 0, rat = 0, rflag = 0;
     const char* hrow = nullptr;

@@ -61,6 +61,11 @@ template <> __device__ __forceinline__ f32x4 mma16<float>(u32x4 a, u32x4 b, f32x
     return c;
 }
 
+// element i of an int32 (es = 4) or int64 (es = 8) array: tokens and lengths arrive in either width
+__device__ __forceinline__ long long int_at(const void* p, int es, size_t i) {
+    return es == 4 ? (long long)reinterpret_cast<const int*>(p)[i] : reinterpret_cast<const long long*>(p)[i];
+}
+
 // wave64 reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

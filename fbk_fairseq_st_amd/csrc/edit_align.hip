@@ -32,9 +32,6 @@ struct EditArgs {
     int a_elem, b_elem, Amax, Bmax, W, cs, ca, cb, collapse;
 };
 
-__device__ __forceinline__ long long tok_at(const void* p, int es, long i) {
-    return es == 4 ? (long long)reinterpret_cast<const int*>(p)[i] : reinterpret_cast<const long long*>(p)[i];
-}
 __device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long x) {
     const uint32_t lo = __shfl_up((uint32_t)x, 1), hi = __shfl_up((uint32_t)(x >> 32), 1);
     return ((unsigned long long)hi << 32) | lo;
@@ -53,7 +50,7 @@ __global__ __launch_bounds__(64 * NW) void edit_align_kernel(const EditArgs p) {
     __shared__ int s_fin[6];
     __shared__ uint32_t s_x[NW][2][6];                              // what lane 63 of a wave hands to lane 0 of the next
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long nq = tok_at(p.a_len, p.a_elem, b), mq = tok_at(p.b_len, p.b_elem, b);
+    const long long nq = int_at(p.a_len, p.a_elem, b), mq = int_at(p.b_len, p.b_elem, b);
     if (nq < 0 || nq > p.Amax || mq < 0 || mq > p.Bmax) { if (tid == 0) p.status[b] = 2; return; }
     int n = (int)nq;
     const int m = (int)mq;
@@ -68,7 +65,7 @@ __global__ __launch_bounds__(64 * NW) void edit_align_kernel(const EditArgs p) {
             unsigned long long last = 0;
             for (int t0 = 0; t0 < n; t0 += 64) {
                 const int t = t0 + lane;
-                const unsigned long long x = t < n ? (unsigned long long)tok_at(arow, p.a_elem, t) : 0ull;
+                const unsigned long long x = t < n ? (unsigned long long)int_at(arow, p.a_elem, t) : 0ull;
                 unsigned long long prev = shfl_up_u64(x);
                 if (lane == 0) prev = last;
                 const bool keep = t < n && (t == 0 || x != prev) && (long long)x != p.blank;
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(64 * NW) void edit_align_kernel(const EditArgs p) {
         int v[K];
         unsigned long long c[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) { bt[k] = j0 + k < m ? tok_at(brow, p.b_elem, j0 + k) : 0; v[k] = 0; c[k] = 0; }
+        for (int k = 0; k < K; ++k) { bt[k] = j0 + k < m ? int_at(brow, p.b_elem, j0 + k) : 0; v[k] = 0; c[k] = 0; }
         int o_cost = 0, pl_cost = 0;
         unsigned long long o_cnt = 0, o_tok = 0, pl_cnt = 0;
         uint32_t o_acc = 0;
@@ -109,8 +106,8 @@ __global__ __launch_bounds__(64 * NW) void edit_align_kernel(const EditArgs p) {
         // wave 0 holds the a tokens of 64 steps in a register, one per lane, and requests the next 64 a group ahead
         unsigned long long acur = 0, anxt = 0;
         if (wave == 0) {
-            if (lane >= 1 && lane - 1 < n) acur = (unsigned long long)tok_at(arow, p.a_elem, lane - 1);
-            if (63 + lane < n) anxt = (unsigned long long)tok_at(arow, p.a_elem, 63 + lane);
+            if (lane >= 1 && lane - 1 < n) acur = (unsigned long long)int_at(arow, p.a_elem, lane - 1);
+            if (63 + lane < n) anxt = (unsigned long long)int_at(arow, p.a_elem, 63 + lane);
         }
         for (int s = 0; s <= steps; ++s) {
             int in_cost = __shfl_up(o_cost, 1);
@@ -125,7 +122,7 @@ __global__ __launch_bounds__(64 * NW) void edit_align_kernel(const EditArgs p) {
             if (wave == 0) {
                 if (s > 0 && (s & 63) == 0) {
                     acur = anxt;
-                    anxt = s + 63 + lane < n ? (unsigned long long)tok_at(arow, p.a_elem, s + 63 + lane) : 0ull;
+                    anxt = s + 63 + lane < n ? (unsigned long long)int_at(arow, p.a_elem, s + 63 + lane) : 0ull;
                 }
                 const unsigned long long t0 = readlane_u64(acur, s & 63);     // a[s - 1]
                 if (lane == 0) { in_cost = s * p.ca; in_cnt = (unsigned long long)s * ONE_A; in_tok = t0; in_acc = 0; }

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(CM_THREADS) void cmvn_kernel(float* x, const void* 
     __shared__ float s_mean[CW], s_inv[CW];
     __shared__ int s_any;
     const int b = blockIdx.x, tid = threadIdx.x, c = tid % CW, g = tid / CW;
-    const long long len = len_elem == 4 ? (long long)reinterpret_cast<const int*>(lengths)[b] : reinterpret_cast<const long long*>(lengths)[b];
+    const long long len = int_at(lengths, len_elem, b);
     const bool refused = len < 0 || len > Tmax;
     const int m = refused || len < 2 ? 0 : (int)len;                // one frame has no variance: no features
     float* xb = x + (size_t)b * Tmax * F;

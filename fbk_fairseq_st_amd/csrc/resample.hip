@@ -53,7 +53,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const RsArgs p) {
     const int tid = threadIdx.x;
     const int b = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
 
-    const long long len = p.len_elem == 4 ? (long long)reinterpret_cast<const int*>(p.lengths)[b] : reinterpret_cast<const long long*>(p.lengths)[b];
+    const long long len = int_at(p.lengths, p.len_elem, b);
     const int rid = p.ratio_id ? p.ratio_id[b] : 0;
     bool refused = len < 0 || len > p.Nmax || rid < 0 || rid >= p.n_banks;
     RsBank d = p.bank[0];

@@ -15,13 +15,13 @@ Hypotheses of at most MAX_HYP tokens (or frames), references of at most MAX_REF.
 import torch
 
 from . import kernels as K
+from .token_rows import as_ints, best_rows, pad_rows
 
 MAX_HYP = K.EDIT_MAX_A                  # S2T_EDIT_MAX_A
 MAX_REF = K.EDIT_MAX_B                  # S2T_EDIT_MAX_B
 OPS = {0: "match", 1: "substitution", 2: "deletion (a reference token left alone)", 3: "insertion (a hypothesis token left alone)"}
 STATUS = {0: "done", 2: "refused: a length outside the padded width"}
 WORKSPACE_LIMIT = 1 << 30               # bytes of step storage one call with ops=True may ask for
-_INTS = (torch.int32, torch.int64)
 _SUMS = ("errors", "substitutions", "insertions", "deletions", "ref_tokens", "sentences")
 
 
@@ -69,27 +69,15 @@ class ErrorRate:
         SequenceGenerator.generate return; the best hypothesis of every sentence is scored (a sentence without one counts as
         empty).  strip_eos: that token is dropped from the end of a hypothesis and of a reference that ends in it."""
         dev = ref.device
-        best = [h[0]["tokens"].to(dev).reshape(-1) if len(h) else torch.empty((0,), dtype=torch.int64, device=dev) for h in hypos]
+        best = best_rows(hypos, dev)
         if len(best) != ref.shape[0]:
             raise ValueError("ErrorRate.score_hypotheses: %d sentences of hypotheses, %d references" % (len(best), ref.shape[0]))
-        dtype = torch.int32 if best and all(t.dtype == torch.int32 for t in best) else torch.int64
-        hyp_len = torch.tensor([t.numel() for t in best], dtype=dtype, device=dev)        # lengths are shapes: no host read
-        width = max([t.numel() for t in best] + [0])
-        hyp = torch.zeros((len(best), width), dtype=dtype, device=dev)
-        if width:
-            hyp = torch.nn.utils.rnn.pad_sequence([t.to(dtype) for t in best], batch_first=True)
-        ref, ref_len = self._ints(ref, ref_len, dev)
+        hyp, hyp_len = pad_rows(best, dev)                              # lengths are shapes: no host read
+        ref, ref_len = as_ints(ref, ref_len, dev)
         if strip_eos is not None:
             hyp_len = _strip(hyp, hyp_len, int(strip_eos))
             ref_len = _strip(ref, ref_len, int(strip_eos))
         return self._run(hyp, hyp_len, ref, ref_len, None, ops)
-
-    @staticmethod
-    def _ints(tok, ln, dev):
-        tok = tok.to(dev)
-        if tok.dtype not in _INTS:
-            tok = tok.long()
-        return tok, ln.to(device=dev, dtype=tok.dtype)
 
     @staticmethod
     def chunk_sentences(hyp_width, ref_width):
@@ -108,8 +96,8 @@ class ErrorRate:
             raise ValueError("ErrorRate: references of at most %d tokens (S2T_EDIT_MAX_B), got a padded width of %d"
                              % (MAX_REF, ref.shape[1]))
         dev = hyp.device
-        hyp, hyp_len = self._ints(hyp, hyp_len, dev)
-        ref, ref_len = self._ints(ref, ref_len, dev)
+        hyp, hyp_len = as_ints(hyp, hyp_len, dev)
+        ref, ref_len = as_ints(ref, ref_len, dev)
         B = hyp.shape[0]
         step = self.chunk_sentences(hyp.shape[1], ref.shape[1]) if ops else max(B, 1)
         parts = [K.edit_align(hyp[s:s + step], hyp_len[s:s + step], ref[s:s + step], ref_len[s:s + step], self.costs,

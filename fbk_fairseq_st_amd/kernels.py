@@ -846,6 +846,33 @@ EDIT_MAX_A = 32767                # S2T_EDIT_MAX_A of include/s2t_hip.h
 EDIT_MAX_B = 4095                 # S2T_EDIT_MAX_B
 
 
+def _token_rows(fn, na, a, a_len, nb, b, b_len):
+    """the opening checks of the wrappers that take two token matrices `na` and `nb`: int32 / int64 [rows, width] each, each with
+    lengths [rows] in its own dtype.  Returns the four contiguous.  (edit_align words both refusals for its one B and keeps them.)"""
+    ints = (torch.int32, torch.int64)
+    if a.dim() != 2 or b.dim() != 2 or a.dtype not in ints or b.dtype not in ints:
+        raise ValueError("%s: %s and %s must be int32 / int64 [rows, width], got %s %s and %s %s"
+                         % (fn, na, nb, a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    if tuple(a_len.shape) != (a.shape[0],) or a_len.dtype != a.dtype or tuple(b_len.shape) != (b.shape[0],) or b_len.dtype != b.dtype:
+        raise ValueError("%s: %s_len must be [%d] and %s_len [%d] in the dtype of their tokens, got %s %s and %s %s"
+                         % (fn, na, a.shape[0], nb, b.shape[0], a_len.dtype, tuple(a_len.shape), b_len.dtype, tuple(b_len.shape)))
+    return a.contiguous(), a_len.contiguous(), b.contiguous(), b_len.contiguous()
+
+
+def _three_ids(fn, pad, eos, unk):
+    """pad, eos and unk as ints; unk < 0 means there is none"""
+    pad, eos, unk = int(pad), int(eos), int(unk)
+    if pad == eos or (unk >= 0 and unk in (pad, eos)):
+        raise ValueError("%s: pad, eos and unk must be three different ids, got %d, %d and %d" % (fn, pad, eos, unk))
+    return pad, eos, unk
+
+
+def _ptr_or(spare):
+    """t -> the address of t, or of the caller's `spare` allocation for an empty t: an empty tensor has no address and the entry
+    points refuse NULL; nothing of a zero-width operand is read or written"""
+    return lambda t: L.ptr(t if t.numel() else spare)
+
+
 def edit_align(a, a_len, b, b_len, costs=(1, 1, 1), collapse_blank=None, want_ops=False):
     """edit-distance alignment of the token rows a [B, Amax] (first a_len[b] entries) to b [B, Bmax] (first b_len[b]) under the
     integer costs (substitution, `a` token left alone, `b` token left alone): include/s2t_hip.h s2t_edit_align states the rule.
@@ -882,9 +909,7 @@ def edit_align(a, a_len, b, b_len, costs=(1, 1, 1), collapse_blank=None, want_op
     a, a_len, b, b_len = a.contiguous(), a_len.contiguous(), b.contiguous(), b_len.contiguous()
     nbytes = int(_lib().s2t_edit_align_workspace(B, Amax, Bmax, 1)) if want_ops else 0
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read or written
-    pad = torch.empty((2,), dtype=torch.int64, device=dev)
-    p = lambda t: L.ptr(t if t.numel() else pad)
+    p = _ptr_or(torch.empty((2,), dtype=torch.int64, device=dev))
     L.check(_lib().s2t_edit_align(p(a), L.ptr(a_len), a.element_size(), p(b), L.ptr(b_len), b.element_size(), B, Amax, Bmax, cs, ca, cb,
                                   int(collapse), int(collapse_blank) if collapse else 0, L.ptr(ws), L.ptr(counts), L.ptr(cost),
                                   L.ptr(status), L.ptr(a_n), p(a_out) if collapse else 0, p(ops) if want_ops else 0,
@@ -904,14 +929,8 @@ def bleu_stats(hyp, hyp_len, ref, ref_len, pad, eos, unk=-1, ref_row=None):
     ref_row: int32 [B], sentence b is scored against row ref_row[b]; None scores row b (then Rrows must be B).  Returns device
     tensors (stats int32 [B, 10] = reflen, predlen, match1, count1, ... match4, count4; status int32 [B], 0 done / 2 refused: a
     length outside its padded width or a ref_row entry outside [0, Rrows), the stats are zeros)."""
-    ints = (torch.int32, torch.int64)
-    if hyp.dim() != 2 or ref.dim() != 2 or hyp.dtype not in ints or ref.dtype not in ints:
-        raise ValueError("bleu_stats: hyp and ref must be int32 / int64 [rows, width], got %s %s and %s %s"
-                         % (hyp.dtype, tuple(hyp.shape), ref.dtype, tuple(ref.shape)))
+    hyp, hyp_len, ref, ref_len = _token_rows("bleu_stats", "hyp", hyp, hyp_len, "ref", ref, ref_len)
     B, Hmax, Rrows, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[0], ref.shape[1]
-    if tuple(hyp_len.shape) != (B,) or hyp_len.dtype != hyp.dtype or tuple(ref_len.shape) != (Rrows,) or ref_len.dtype != ref.dtype:
-        raise ValueError("bleu_stats: hyp_len must be [%d] and ref_len [%d] in the dtype of their tokens, got %s %s and %s %s"
-                         % (B, Rrows, hyp_len.dtype, tuple(hyp_len.shape), ref_len.dtype, tuple(ref_len.shape)))
     if ref_row is None:
         if Rrows != B:
             raise ValueError("bleu_stats: %d hypotheses and %d references need a ref_row map" % (B, Rrows))
@@ -919,18 +938,13 @@ def bleu_stats(hyp, hyp_len, ref, ref_len, pad, eos, unk=-1, ref_row=None):
         raise ValueError("bleu_stats: ref_row must be int32 [%d], got %s %s" % (B, ref_row.dtype, tuple(ref_row.shape)))
     if Hmax > BLEU_MAX_LEN or Rmax > BLEU_MAX_LEN:
         raise ValueError("bleu_stats: padded widths of at most %d (S2T_BLEU_MAX_LEN), got %d and %d" % (BLEU_MAX_LEN, Hmax, Rmax))
-    pad, eos, unk = int(pad), int(eos), int(unk)
-    if pad == eos or (unk >= 0 and unk in (pad, eos)):
-        raise ValueError("bleu_stats: pad, eos and unk must be three different ids, got %d, %d and %d" % (pad, eos, unk))
+    pad, eos, unk = _three_ids("bleu_stats", pad, eos, unk)
     dev = hyp.device
     stats = torch.zeros((B, 10), dtype=torch.int32, device=dev)
     status = torch.zeros((B,), dtype=torch.int32, device=dev)
     if B == 0:
         return stats, status
-    hyp, hyp_len, ref, ref_len = hyp.contiguous(), hyp_len.contiguous(), ref.contiguous(), ref_len.contiguous()
-    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read
-    fill = torch.zeros((2,), dtype=torch.int64, device=dev)
-    p = lambda t: L.ptr(t if t.numel() else fill)
+    p = _ptr_or(torch.zeros((2,), dtype=torch.int64, device=dev))
     L.check(_lib().s2t_bleu_stats(p(hyp), L.ptr(hyp_len), hyp.element_size(), p(ref), p(ref_len), ref.element_size(),
                                   L.ptr(ref_row.contiguous()) if ref_row is not None else 0, B, Hmax, Rmax, Rrows, pad, eos, unk,
                                   L.ptr(stats), L.ptr(status), L.stream()), "s2t_bleu_stats")
@@ -959,14 +973,8 @@ def bleu_pairs(cand, cand_len, cand_sent, ref, ref_len, ref_off, pad, eos, unk=-
     shapes; None reads it from ref_off (a host read).  Returns device tensors (stats int32 [Rc, M, 10], status int32 [Rc, M]: 0 done,
     2 refused -- a length outside its padded width, a sentence outside [0, B), offsets that descend, leave [0, Rr] or span more than
     M rows; zeros, and zeros behind a sentence's list)."""
-    ints = (torch.int32, torch.int64)
-    if cand.dim() != 2 or ref.dim() != 2 or cand.dtype not in ints or ref.dtype not in ints:
-        raise ValueError("bleu_pairs: cand and ref must be int32 / int64 [rows, width], got %s %s and %s %s"
-                         % (cand.dtype, tuple(cand.shape), ref.dtype, tuple(ref.shape)))
+    cand, cand_len, ref, ref_len = _token_rows("bleu_pairs", "cand", cand, cand_len, "ref", ref, ref_len)
     Rc, Hmax, Rr, Pmax = cand.shape[0], cand.shape[1], ref.shape[0], ref.shape[1]
-    if tuple(cand_len.shape) != (Rc,) or cand_len.dtype != cand.dtype or tuple(ref_len.shape) != (Rr,) or ref_len.dtype != ref.dtype:
-        raise ValueError("bleu_pairs: cand_len must be [%d] and ref_len [%d] in the dtype of their tokens, got %s %s and %s %s"
-                         % (Rc, Rr, cand_len.dtype, tuple(cand_len.shape), ref_len.dtype, tuple(ref_len.shape)))
     if tuple(cand_sent.shape) != (Rc,) or cand_sent.dtype != torch.int32:
         raise ValueError("bleu_pairs: cand_sent must be int32 [%d], got %s %s" % (Rc, cand_sent.dtype, tuple(cand_sent.shape)))
     if ref_off.dim() != 1 or ref_off.shape[0] < 1 or ref_off.dtype != torch.int32:
@@ -979,18 +987,13 @@ def bleu_pairs(cand, cand_len, cand_sent, ref, ref_len, ref_off, pad, eos, unk=-
     M = int(max_list)
     if not 0 <= M <= MBR_MAX_LIST:
         raise ValueError("bleu_pairs: lists of at most %d pseudo-references (S2T_MBR_MAX_LIST), got %d" % (MBR_MAX_LIST, M))
-    pad, eos, unk = int(pad), int(eos), int(unk)
-    if pad == eos or (unk >= 0 and unk in (pad, eos)):
-        raise ValueError("bleu_pairs: pad, eos and unk must be three different ids, got %d, %d and %d" % (pad, eos, unk))
+    pad, eos, unk = _three_ids("bleu_pairs", pad, eos, unk)
     dev = cand.device
     stats = torch.empty((Rc, M, 10), dtype=torch.int32, device=dev)      # the kernel writes every element
     status = torch.empty((Rc, M), dtype=torch.int32, device=dev)
     if Rc == 0 or M == 0:
         return stats, status
-    cand, cand_len, ref, ref_len = cand.contiguous(), cand_len.contiguous(), ref.contiguous(), ref_len.contiguous()
-    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read
-    fill = torch.zeros((2,), dtype=torch.int64, device=dev)
-    p = lambda t: L.ptr(t if t.numel() else fill)
+    p = _ptr_or(torch.zeros((2,), dtype=torch.int64, device=dev))
     L.check(_lib().s2t_bleu_pairs(p(cand), L.ptr(cand_len), cand.element_size(), p(ref), p(ref_len), ref.element_size(),
                                   L.ptr(cand_sent.contiguous()), L.ptr(ref_off.contiguous()), Rc, B, Hmax, Pmax, Rr, M, pad, eos, unk,
                                   L.ptr(stats), L.ptr(status), L.stream()), "s2t_bleu_pairs")
@@ -1015,14 +1018,8 @@ def chrf_stats(hyp, hyp_len, ref, ref_len, pieces, piece_off, unk=-1, char_order
     = hyp_n, ref_n, match_n of the character orders 1 .. 6 and the word orders 1 .. 2, zeros above the configured orders; status
     int32 [P], 0 done / 2 refused: a map entry outside its matrix, a length outside its padded width, a token outside [0, V), a side
     of more than CHRF_MAX_CHARS characters; the stats are zeros)."""
-    ints = (torch.int32, torch.int64)
-    if hyp.dim() != 2 or ref.dim() != 2 or hyp.dtype not in ints or ref.dtype not in ints:
-        raise ValueError("chrf_stats: hyp and ref must be int32 / int64 [rows, width], got %s %s and %s %s"
-                         % (hyp.dtype, tuple(hyp.shape), ref.dtype, tuple(ref.shape)))
+    hyp, hyp_len, ref, ref_len = _token_rows("chrf_stats", "hyp", hyp, hyp_len, "ref", ref, ref_len)
     Hrows, Hmax, Rrows, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[0], ref.shape[1]
-    if tuple(hyp_len.shape) != (Hrows,) or hyp_len.dtype != hyp.dtype or tuple(ref_len.shape) != (Rrows,) or ref_len.dtype != ref.dtype:
-        raise ValueError("chrf_stats: hyp_len must be [%d] and ref_len [%d] in the dtype of their tokens, got %s %s and %s %s"
-                         % (Hrows, Rrows, hyp_len.dtype, tuple(hyp_len.shape), ref_len.dtype, tuple(ref_len.shape)))
     for name, m in (("hyp_row", hyp_row), ("ref_row", ref_row)):
         if m is not None and (m.dim() != 1 or m.dtype != torch.int32):
             raise ValueError("chrf_stats: %s must be int32 [pairs], got %s %s" % (name, m.dtype, tuple(m.shape)))
@@ -1051,10 +1048,7 @@ def chrf_stats(hyp, hyp_len, ref, ref_len, pieces, piece_off, unk=-1, char_order
     status = torch.empty((P,), dtype=torch.int32, device=dev)
     if P == 0:
         return stats, status
-    hyp, hyp_len, ref, ref_len = hyp.contiguous(), hyp_len.contiguous(), ref.contiguous(), ref_len.contiguous()
-    # an empty tensor has no address and the entry point refuses NULL; nothing of a zero-width operand is read
-    fill = torch.zeros((2,), dtype=torch.int64, device=dev)
-    p = lambda t: L.ptr(t if t.numel() else fill)
+    p = _ptr_or(torch.zeros((2,), dtype=torch.int64, device=dev))
     L.check(_lib().s2t_chrf_stats(p(hyp), p(hyp_len), hyp.element_size(), p(ref), p(ref_len), ref.element_size(),
                                   L.ptr(hyp_row.contiguous()) if hyp_row is not None else 0,
                                   L.ptr(ref_row.contiguous()) if ref_row is not None else 0, P, Hmax, Rmax, Hrows, Rrows,

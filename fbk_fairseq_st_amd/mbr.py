@@ -24,13 +24,13 @@ MAX_LIST pseudo-references per sentence.
 import torch
 
 from . import kernels as K
-from .bleu_scorer import _pad_rows, sentence_bleu
+from .bleu_scorer import sentence_bleu
+from .token_rows import as_ints, pad_rows
 
 MAX_LEN = K.MBR_MAX_LEN                 # S2T_MBR_MAX_LEN
 MAX_LIST = K.MBR_MAX_LIST               # S2T_MBR_MAX_LIST
 OUTPUT_LIMIT = 1 << 30                  # bytes of stats and status one kernel call may ask for: above it a batch is cut by sentences
 STATUS = {0: "done", 2: "refused: a length outside the padded width, a sentence outside the batch, or offsets that are no list"}
-_INTS = (torch.int32, torch.int64)
 _CHRF_PAIR_BYTES = 4 * K.CHRF_STATS + 4 + 8 + 8      # stats, status, the two row maps and the float64 score of a pair of the chrF utility
 
 
@@ -130,11 +130,11 @@ class MBRDecoder:
         nc, nr = [len(h) for h in hypos], [len(p) for p in pseudo]
         if sum(nc) == 0:
             return None
-        cand, cand_len = _pad_rows([h["tokens"].to(dev).reshape(-1) for hs in hypos for h in hs], dev)
+        cand, cand_len = pad_rows([h["tokens"].to(dev).reshape(-1) for hs in hypos for h in hs], dev)
         if same:
             ref, ref_len = cand, cand_len
         else:
-            ref, ref_len = _pad_rows([h["tokens"].to(dev).reshape(-1) for hs in pseudo for h in hs], dev)
+            ref, ref_len = pad_rows([h["tokens"].to(dev).reshape(-1) for hs in pseudo for h in hs], dev)
         cand_sent = torch.tensor([b for b, n in enumerate(nc) for _ in range(n)], dtype=torch.int32, device=dev)   # lists' shapes
         off = [0]
         for n in nr:
@@ -229,8 +229,8 @@ class MBRDecoder:
                              % (MAX_LEN, cand.shape[1], ref.shape[1]))
         dev = cand.device
         same = ref is cand
-        cand, cand_len = _ints(cand, cand_len, dev)
-        ref, ref_len = (cand, cand_len) if same else _ints(ref, ref_len, dev)
+        cand, cand_len = as_ints(cand, cand_len, dev)
+        ref, ref_len = (cand, cand_len) if same else as_ints(ref, ref_len, dev)
         cand_sent, ref_off = cand_sent.to(device=dev, dtype=torch.int32), ref_off.to(device=dev, dtype=torch.int32)
         stats, status = K.bleu_pairs(cand, cand_len, cand_sent, ref, ref_len, ref_off, self.pad, self.eos, self.unk, max_list=max_list)
         Rc, M = status.shape
@@ -269,10 +269,3 @@ class MBRDecoder:
             0, slot, torch.where(gain == top[slot], rows, torch.full_like(rows, Rc)), "amin")
         best = torch.where(first[:B] < Rc, first[:B], torch.full_like(first[:B], -1))
         return {"stats": stats, "status": status, "utility": utility, "gain": gain, "best": best}
-
-
-def _ints(tok, ln, dev):
-    tok = tok.to(dev)
-    if tok.dtype not in _INTS:
-        tok = tok.long()
-    return tok, ln.to(device=dev, dtype=tok.dtype)

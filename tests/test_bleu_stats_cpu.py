@@ -258,3 +258,47 @@ def test_value_errors(calls):
         bs.score(ok, n1, torch.zeros(2, 3).long(), torch.tensor([3, 3]))
     assert calls == [] and bs.result() == EMPTY, "nothing was scored"
     assert math.isinf(BS._corpus([0, 3, 0, 3, 0, 2, 0, 1, 0, 0], 4)["ratio"])
+
+
+# ------------------------------------------------------------------ token_rows: what the four scorers share
+def test_token_rows_dtypes_and_empty_lists():
+    from fbk_fairseq_st_amd import token_rows as TR
+    for dt, want in ((torch.int32, torch.int32), (torch.int64, torch.int64), (torch.int16, torch.int64), (torch.uint8, torch.int64),
+                     (torch.float32, torch.int64)):
+        tok, ln = TR.as_ints(torch.tensor([[4, 5], [6, 7]]).to(dt), torch.tensor([2, 1], dtype=torch.int16), "cpu")
+        assert tok.dtype == want and ln.dtype == want and tok.tolist() == [[4, 5], [6, 7]] and ln.tolist() == [2, 1], dt
+    t = lambda dt, *v: torch.tensor(v, dtype=dt)
+    mat, ln = TR.pad_rows([t(torch.int32, 4, 5, 6), t(torch.int32), t(torch.int32, 7)], "cpu")
+    assert mat.dtype == ln.dtype == torch.int32 and mat.tolist() == [[4, 5, 6], [0, 0, 0], [7, 0, 0]] and ln.tolist() == [3, 0, 1]
+    mat, ln = TR.pad_rows([t(torch.int32, 4, 5), t(torch.int64, 7)], "cpu")                # one row that is not int32: int64
+    assert mat.dtype == ln.dtype == torch.int64 and mat.tolist() == [[4, 5], [7, 0]] and ln.tolist() == [2, 1]
+    mat, ln = TR.pad_rows([], "cpu")
+    assert tuple(mat.shape) == (0, 0) and tuple(ln.shape) == (0,) and mat.dtype == ln.dtype == torch.int64
+    mat, ln = TR.pad_rows([t(torch.int32), t(torch.int32)], "cpu")                         # rows without tokens: width 0
+    assert tuple(mat.shape) == (2, 0) and ln.tolist() == [0, 0] and mat.dtype == torch.int32
+    best = TR.best_rows([[{"tokens": t(torch.int32, 4, 5)}, {"tokens": t(torch.int32, 9)}], [], [{"tokens": t(torch.int64, 6).reshape(1, 1)}]], "cpu")
+    assert [b.tolist() for b in best] == [[4, 5], [], [6]] and [b.dtype for b in best] == [torch.int32, torch.int64, torch.int64]
+
+
+def test_nbest_tables_with_a_stub_run():
+    """the helper of both score_nbest methods on a run() that needs no kernel: the flat list it hands over, the scatter, the first
+    maximum, the picked sums; and a batch without sentences, which the scorers' tests do not reach"""
+    from fbk_fairseq_st_amd import token_rows as TR
+    t = lambda *v: torch.tensor(v, dtype=torch.int64)
+    hypos = [[{"tokens": t(4, 5)}, {"tokens": t(9, 9, 9)}, {"tokens": t(9, 9, 9)}], [], [{"tokens": t(7)}]]
+    seen = []
+
+    def run(hyp, hyp_len, rows):                                   # stats: (first token, length, row), the score is the length
+        seen.append((hyp.tolist(), hyp_len.tolist(), rows.tolist(), rows.dtype))
+        stats = torch.stack([hyp[:, :1].sum(1).int(), hyp_len.int(), rows], 1)
+        return {"stats": stats, "status": torch.full((hyp.shape[0],), 2, dtype=torch.int32), "points": hyp_len.double()}
+    stats, status, score, n_hyp, oracle, pick = TR.nbest_tables(hypos, 3, "cpu", run, 3, "points")
+    assert seen == [([[4, 5, 0], [9, 9, 9], [9, 9, 9], [7, 0, 0]], [2, 3, 3, 1], [0, 0, 0, 2], torch.int32)]
+    assert stats.dtype == status.dtype == torch.int32 and score.dtype == torch.float64 and n_hyp.dtype == oracle.dtype == torch.int64
+    assert stats.tolist() == [[[4, 2, 0], [9, 3, 0], [9, 3, 0]], [[0, 0, 0]] * 3, [[7, 1, 2], [0, 0, 0], [0, 0, 0]]]
+    assert status.tolist() == [[2, 2, 2], [0, 0, 0], [2, 0, 0]] and score.tolist() == [[2, 3, 3], [-1, -1, -1], [1, -1, -1]]
+    assert n_hyp.tolist() == [3, 0, 1] and oracle.tolist() == [1, 0, 0], "the first of two equal maxima; 0 for an empty list"
+    assert pick("best").tolist() == [11, 3, 2] and pick("oracle").tolist() == [16, 4, 2] and pick("best").dtype == torch.int64
+    stats, status, score, n_hyp, oracle, pick = TR.nbest_tables([], 0, "cpu", run, 3, "points")
+    assert tuple(stats.shape) == (0, 1, 3) and tuple(score.shape) == (0, 1) and tuple(oracle.shape) == (0,) and oracle.dtype == torch.int64
+    assert seen[-1][0] == [] and n_hyp.tolist() == []

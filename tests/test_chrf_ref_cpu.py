@@ -130,3 +130,20 @@ def test_every_wrong_twin_differs_from_the_reference():
     print("pairs %d, differing per twin: %s" % (pairs, differs))
     assert sorted(differs) == sorted(R.TWINS) and len(R.TWINS) >= 5
     assert all(n > 0 for n in differs.values()), differs
+
+
+def test_characters_of_one_code_point_a_token_count_as_bleu_tokens():
+    """the identity tests/test_ngram_match_gpu.py holds the two kernels to, on its own pairs and on the two references alone: with one
+    character a token and nothing trimmed, chrF's character statistics of the orders 1 to 4 are BLEU's; and BLEU's two forms agree"""
+    import bleu_ref
+    import ngram_cases as G
+    n = 0
+    for call in range(len(G.HYP_LENS)):
+        hyps, refs, bleu, chrf = G.case(call)
+        for h, r, b in zip(hyps, refs, bleu):
+            assert list(b) == bleu_ref.stats_positional(h, r, G.PAD, G.EOS, -1)
+        assert (chrf[:, 0] == bleu[:, 1]).all() and (chrf[:, 1] == bleu[:, 0]).all()
+        for k in range(4):
+            assert (chrf[:, 3 * k + 2] == bleu[:, 2 + 2 * k]).all() and (chrf[:, 3 * k] == bleu[:, 3 + 2 * k]).all()
+        n += len(hyps)
+    assert n == 210
