@@ -67,6 +67,35 @@ def piece_table(dictionary, bpe="sentencepiece"):
             "unk": int(dictionary.unk()), "bpe": bpe}
 
 
+class DeviceTable:
+    """what `piece_table` returns, checked once and copied to each device once: the part ChrfScorer and TextErrorRate share.  who: the
+    owner's name in the errors.  Also the table's extremes, which bound a row's units from its token width without a device read:
+    `max_chars` (the characters of the longest piece), `max_breaks` (the most breaks in one piece) and `max_spaced` (the most
+    characters plus breaks in one piece); entry V, the reference-side unk, is among them."""
+
+    def __init__(self, table, who):
+        pieces, off = np.asarray(table["pieces"]), np.asarray(table["piece_off"])
+        self.V, self.unk = int(table["V"]), int(table["unk"])
+        if pieces.dtype != np.uint32 or off.dtype != np.int32 or off.shape != (self.V + 2,) or not self.unk < self.V:
+            raise ValueError("%s: the table is what piece_table returns: pieces uint32, piece_off int32 [V + 2], unk < V; got %s, %s %s, "
+                             "V = %d, unk = %d" % (who, pieces.dtype, off.dtype, off.shape, self.V, self.unk))
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != pieces.shape[0]:
+            raise ValueError("%s: piece_off must rise from 0 to the %d elements of pieces" % (who, pieces.shape[0]))
+        breaks = np.concatenate([[0], np.cumsum(pieces == SEP)])[off]           # the breaks in front of every piece
+        self.max_breaks = int(np.diff(breaks).max())
+        self.max_chars = int((np.diff(off) - np.diff(breaks)).max())
+        self.max_spaced = int(np.diff(off).max())
+        self._host = (torch.from_numpy(pieces.view(np.int32).copy()), torch.from_numpy(off.copy()))
+        self._on = {}
+
+    def on(self, dev):
+        """the table's two tensors on dev: copied there once"""
+        key = str(dev)
+        if key not in self._on:
+            self._on[key] = tuple(t.to(dev) for t in self._host)
+        return self._on[key]
+
+
 class ChrfScorer:
     """table: what `piece_table` returns.  char_order 1 .. 6 and word_order 0 .. 2 (chrF is 6 and 0, chrF++ 6 and 2); beta weighs
     recall over precision.  A reference-side unk is rendered as the table's entry V and so matches nothing a hypothesis can hold."""
@@ -79,15 +108,8 @@ class ChrfScorer:
             raise ValueError("ChrfScorer: word_order from 0 to %d (S2T_CHRF_MAX_WORD_ORDER), got %r" % (K.CHRF_MAX_WORD_ORDER, word_order))
         if not self.beta > 0:
             raise ValueError("ChrfScorer: beta must be positive, got %r" % (beta,))
-        pieces, off = np.asarray(table["pieces"]), np.asarray(table["piece_off"])
-        self.V, self.unk = int(table["V"]), int(table["unk"])
-        if pieces.dtype != np.uint32 or off.dtype != np.int32 or off.shape != (self.V + 2,) or not self.unk < self.V:
-            raise ValueError("ChrfScorer: the table is what piece_table returns: pieces uint32, piece_off int32 [V + 2], unk < V; got %s, %s %s, "
-                             "V = %d, unk = %d" % (pieces.dtype, off.dtype, off.shape, self.V, self.unk))
-        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != pieces.shape[0]:
-            raise ValueError("ChrfScorer: piece_off must rise from 0 to the %d elements of pieces" % pieces.shape[0])
-        self._host = (torch.from_numpy(pieces.view(np.int32).copy()), torch.from_numpy(off.copy()))
-        self._table = {}
+        self.table = DeviceTable(table, "ChrfScorer")
+        self.V, self.unk = self.table.V, self.table.unk
         self._acc = None
 
     @classmethod
@@ -96,10 +118,7 @@ class ChrfScorer:
 
     def table_on(self, dev):
         """the table's two tensors on dev: copied there once"""
-        key = str(dev)
-        if key not in self._table:
-            self._table[key] = tuple(t.to(dev) for t in self._host)
-        return self._table[key]
+        return self.table.on(dev)
 
     # ------------------------------------------------------------------ scoring
     @torch.no_grad()

@@ -1057,6 +1057,60 @@ def chrf_stats(hyp, hyp_len, ref, ref_len, pieces, piece_off, unk=-1, char_order
     return stats, status
 
 
+TEXT_MAX_UNITS = 4095             # S2T_TEXT_MAX_UNITS of include/s2t_hip.h: units per side, = EDIT_MAX_B = CHRF_MAX_CHARS
+TEXT_MODES = {"word": 0, "char": 1, "char_nospace": 2}      # the `mode` of s2t_text_units
+
+
+def text_units(hyp, hyp_len, ref, ref_len, pieces, piece_off, unk, mode, hyp_width, ref_width, hyp_row=None, ref_row=None):
+    """unit rows of pairs of token rows, hyp [Hrows, Hmax] (first hyp_len[r] entries) against ref [Rrows, Rmax]: include/s2t_hip.h
+    s2t_text_units states the rule.  mode: 0 words (first-equal-occurrence ids over both sides of the pair), 1 characters with one
+    space between words, 2 characters without (TEXT_MODES).  hyp_width / ref_width: the widths Uh / Ur of the unit rows, at most
+    TEXT_MAX_UNITS.  Tokens, lengths, the piece table, unk and the row maps are those of `chrf_stats`.  Returns device tensors
+    (hyp_units int32 [P, Uh], hyp_n int32 [P], ref_units int32 [P, Ur], ref_n int32 [P], status int32 [P]: 0 done / 2 refused --
+    what chrf_stats refuses, or a side with more units than its width; hyp_n = ref_n = 0 then).  Entries of the unit rows behind
+    hyp_n / ref_n are not written."""
+    hyp, hyp_len, ref, ref_len = _token_rows("text_units", "hyp", hyp, hyp_len, "ref", ref, ref_len)
+    Hrows, Hmax, Rrows, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[0], ref.shape[1]
+    for name, m in (("hyp_row", hyp_row), ("ref_row", ref_row)):
+        if m is not None and (m.dim() != 1 or m.dtype != torch.int32):
+            raise ValueError("text_units: %s must be int32 [pairs], got %s %s" % (name, m.dtype, tuple(m.shape)))
+    P = hyp_row.shape[0] if hyp_row is not None else ref_row.shape[0] if ref_row is not None else Hrows
+    if (hyp_row is not None and hyp_row.shape[0] != P) or (ref_row is not None and ref_row.shape[0] != P):
+        raise ValueError("text_units: hyp_row and ref_row must both be int32 [%d], got %s and %s" % (P, tuple(hyp_row.shape), tuple(ref_row.shape)))
+    if (hyp_row is None and Hrows != P) or (ref_row is None and Rrows != P):
+        raise ValueError("text_units: %d pairs of %d hypothesis rows and %d reference rows need a row map for the side that has not %d rows"
+                         % (P, Hrows, Rrows, P))
+    if Hmax > CHRF_MAX_LEN or Rmax > CHRF_MAX_LEN:
+        raise ValueError("text_units: padded widths of at most %d tokens (S2T_CHRF_MAX_LEN), got %d and %d" % (CHRF_MAX_LEN, Hmax, Rmax))
+    mode, Uh, Ur, unk = int(mode), int(hyp_width), int(ref_width), int(unk)
+    if mode not in TEXT_MODES.values():
+        raise ValueError("text_units: mode is 0 (words), 1 (characters with spaces) or 2 (characters without), got %d" % mode)
+    if not (0 <= Uh <= TEXT_MAX_UNITS and 0 <= Ur <= TEXT_MAX_UNITS):
+        raise ValueError("text_units: unit widths from 0 to %d (S2T_TEXT_MAX_UNITS), got %d and %d" % (TEXT_MAX_UNITS, Uh, Ur))
+    if pieces.dim() != 1 or pieces.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or piece_off.dim() != 1 or piece_off.dtype != torch.int32 \
+            or piece_off.shape[0] < 2:
+        raise ValueError("text_units: the piece table is pieces (int32 / uint32 [n]) and piece_off (int32 [V + 2]), got %s %s and %s %s"
+                         % (pieces.dtype, tuple(pieces.shape), piece_off.dtype, tuple(piece_off.shape)))
+    V = piece_off.shape[0] - 2
+    if unk >= V:
+        raise ValueError("text_units: unk must be a token of the table's %d (or negative), got %d" % (V, unk))
+    dev = hyp.device
+    hyp_units = torch.empty((P, Uh), dtype=torch.int32, device=dev)          # written up to hyp_n
+    ref_units = torch.empty((P, Ur), dtype=torch.int32, device=dev)
+    hyp_n = torch.empty((P,), dtype=torch.int32, device=dev)                 # the kernel writes every element of these three
+    ref_n = torch.empty((P,), dtype=torch.int32, device=dev)
+    status = torch.empty((P,), dtype=torch.int32, device=dev)
+    if P == 0:
+        return hyp_units, hyp_n, ref_units, ref_n, status
+    p = _ptr_or(torch.zeros((2,), dtype=torch.int64, device=dev))
+    L.check(_lib().s2t_text_units(p(hyp), p(hyp_len), hyp.element_size(), p(ref), p(ref_len), ref.element_size(),
+                                  L.ptr(hyp_row.contiguous()) if hyp_row is not None else 0,
+                                  L.ptr(ref_row.contiguous()) if ref_row is not None else 0, P, Hmax, Rmax, Hrows, Rrows,
+                                  p(pieces.contiguous()), L.ptr(piece_off.contiguous()), pieces.shape[0], V, unk, mode, Uh, Ur,
+                                  p(hyp_units), p(ref_units), L.ptr(hyp_n), L.ptr(ref_n), L.ptr(status), L.stream()), "s2t_text_units")
+    return hyp_units, hyp_n, ref_units, ref_n, status
+
+
 FBANK_MAX_BINS = 128              # S2T_FBANK_MAX_BINS of include/s2t_hip.h
 FBANK_TILE_ELEMS = 8192           # S2T_FBANK_TILE_ELEMS: a workgroup takes FBANK_TILE_ELEMS // N consecutive frames
 FBANK_FFT_SIZES = (256, 512, 1024)

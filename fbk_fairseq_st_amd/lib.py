@@ -75,6 +75,8 @@ SIGNATURES = {
     "s2t_bleu_stats": [P, P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, P, P, P],
     "s2t_bleu_pairs": [P, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, P, P, P],
     "s2t_chrf_stats": [P, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_longlong, c_int, c_int, P, P, P],
+    "s2t_text_units": [P, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_longlong, c_int, c_int, c_int,
+                       P, P, P, P, P, P],
     "s2t_fbank": [P, c_int, c_longlong, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_double, P, P, P, P],
     "s2t_cmvn": [P, P, c_int, c_int, c_int, c_int, P, P, P],
     "s2t_resample": [P, c_int, c_longlong, P, c_int, P, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P, P, P],

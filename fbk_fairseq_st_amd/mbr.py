@@ -15,7 +15,11 @@ its pseudo-references: nothing is left out.  A hypothesis that contains `unk` th
 reference-side `unk` matches nothing: that is the reference's rule for references, kept as it is.
 
 With `utility=ChrfScorer(...)` the utility of a pair is instead the chrF of the two detokenised texts (chrf_scorer.py):
-the pairs of a sentence go through `ChrfScorer.score_pairs` on two device row maps, and `mbr_score` is in chrF percent.
+the pairs of a sentence go through `ChrfScorer.score_pairs` on two device row maps, and `mbr_score` is in chrF percent.  With
+`utility=TextErrorRate(...)` (text_error_rate.py) it is the word or character accuracy of the candidate's text against
+the pseudo-reference's, 100 - min(error rate, 100): the classic MBR for speech recognition, by expected word error.  A utility
+object has `score_pairs` and may name the pair score it returns (`utility_key`; "sentence_chrf" without one) and the bytes a pair
+costs (`pair_bytes`); the score lies in [0, 100] with 0 worst.
 
 The hot path is csrc/bleu_pairs.hip (kernels.bleu_pairs; include/s2t_hip.h states the operands, the rule is s2t_bleu_stats's): one
 launch for all pairs of a call, no copies of the lists, no host read.  Padded widths of at most MAX_LEN tokens, lists of at most
@@ -45,7 +49,8 @@ class MBRDecoder:
     utility: None for the sentence BLEU over token ids described above, or a `ChrfScorer`: then the utility of a pair is the
     scorer's `sentence_chrf` of the two texts (chrf_scorer.py; its `score_pairs` on two device row maps built from the lists'
     shapes, one launch of kernels.chrf_stats per cut), `mbr_score` is in chrF percent, and the pairs the kernel refuses count for
-    nothing.  The scorer's accumulator takes the pairs' sums as with any `score_pairs` call."""
+    nothing.  The scorer's accumulator takes the pairs' sums as with any `score_pairs` call.  A `TextErrorRate` takes the same
+    route with its `sentence_accuracy` (two launches per cut); `mbr_score` is then the expected accuracy in percent."""
 
     def __init__(self, generator, pad, eos, unk=-1, weights="uniform", utility=None):
         self.generator = generator
@@ -89,7 +94,7 @@ class MBRDecoder:
         weights = self.weights if weights is None else weights
         dev = next((h["tokens"].device for hs in list(hypos) + list(pseudo) for h in hs), torch.device("cpu"))
         out = [[] for _ in range(B)]
-        for b0, b1 in self.chunk_sentences(nc, nr, 44 if self.utility is None else _CHRF_PAIR_BYTES):
+        for b0, b1 in self.chunk_sentences(nc, nr, self._pair_bytes(hypos, pseudo)):
             gain = self._gains(hypos[b0:b1], pseudo[b0:b1], same, weights, b0, B, dev)
             if gain is None:
                 continue
@@ -108,6 +113,16 @@ class MBRDecoder:
                     out[b].append(h)
                 at += nc[b]
         return out
+
+    def _pair_bytes(self, hypos, pseudo):
+        """what a call writes per pair: 44 for the BLEU kernel, else the utility's `pair_bytes` -- a number, or a function of the two
+        token widths (the longest candidate and pseudo-reference: shapes, no device read) -- and _CHRF_PAIR_BYTES without one"""
+        if self.utility is None:
+            return 44
+        per = getattr(self.utility, "pair_bytes", _CHRF_PAIR_BYTES)
+        if callable(per):
+            per = per(max([h["tokens"].numel() for hs in hypos for h in hs] + [0]), max([h["tokens"].numel() for hs in pseudo for h in hs] + [0]))
+        return int(per)
 
     @staticmethod
     def chunk_sentences(nc, nr, pair_bytes=44):
@@ -195,7 +210,7 @@ class MBRDecoder:
         got = self.utility.score_pairs(cand, cand_len, hyp_row.int(), ref, ref_len, ref_row.int())
         utility = torch.zeros((Rc, M), dtype=torch.float64, device=dev)
         counts = torch.zeros((Rc, M), dtype=torch.bool, device=dev)
-        utility[hyp_row, k] = got["sentence_chrf"]
+        utility[hyp_row, k] = got[getattr(self.utility, "utility_key", "sentence_chrf")]
         counts[hyp_row, k] = got["status"] == 0
         if weights is None:
             w = counts.double()

@@ -31,12 +31,14 @@ def best_rows(hypos, dev):
     return [h[0]["tokens"].to(dev).reshape(-1) if len(h) else torch.empty((0,), dtype=torch.int64, device=dev) for h in hypos]
 
 
-def nbest_tables(hypos, B, dev, run, width, key):
+def nbest_tables(hypos, B, dev, run, width, key, lowest=False):
     """Every hypothesis of B sentences through one call.  run(hyp, hyp_len, rows) scores the flat list (rows: int32, the sentence of
     every hypothesis) and returns a dict with `stats` [n, width], `status` [n] and the float64 score `key` [n].  Returns
     (stats [B, N, width], status [B, N], score [B, N], n_hyp [B], oracle [B], pick): N the longest list, at least 1; zeros, and -1 in
     the score, behind a list's end; oracle the first index of the row's highest score (0 for an empty list); pick(which) the int64
-    sums [width] of the stats of hypothesis 0 ("best") or oracle[b] ("oracle") over the sentences."""
+    sums [width] of the stats of hypothesis 0 ("best") or oracle[b] ("oracle") over the sentences.  lowest: the score is an error
+    rate -- oracle is the first index of the row's lowest score among its finished entries (status 0; a refused entry's score of 0
+    is no result), 0 for a list without one."""
     counts = [len(h) for h in hypos]
     N = max(counts + [1])
     flat = [h["tokens"].to(dev).reshape(-1) for hs in hypos for h in hs]
@@ -51,7 +53,10 @@ def nbest_tables(hypos, B, dev, run, width, key):
     score = torch.full((B, N), -1.0, dtype=torch.float64, device=dev)
     stats[at], status[at], score[at] = got["stats"], got["status"], got[key]
     cols = torch.arange(N, device=dev).expand(B, N)                            # the first index of the row's maximum
-    oracle = torch.where(score == score.max(1, keepdim=True).values, cols, torch.full_like(cols, N)).min(1).values if B else \
+    rank = score
+    if lowest:                                                                 # ... of the lowest score that is a result
+        rank = torch.where((score >= 0) & (status == 0), -score, torch.full_like(score, float("-inf")))
+    oracle = torch.where(rank == rank.max(1, keepdim=True).values, cols, torch.full_like(cols, N)).min(1).values if B else \
         torch.zeros((0,), dtype=torch.int64, device=dev)
 
     def pick(which):

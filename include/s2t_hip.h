@@ -614,6 +614,43 @@ int s2t_chrf_stats(const void* hyp, const void* hyp_len, int hyp_elem, const voi
                    const int* hyp_row, const int* ref_row, int P, int Hmax, int Rmax, int Hrows, int Rrows,
                    const unsigned int* pieces, const int* piece_off, int n_pieces, int V, long long unk, int char_order,
                    int word_order, int* stats, int* status, void* stream);
+/* ---- Unit rows of detokenised token rows (csrc/text_units.hip): per pair of rows the words or the characters of the two texts as
+ * int32 rows that s2t_edit_align takes, so that WER and CER of the text come from two launches without a host read.
+ * Text of a row: as in s2t_chrf_stats above, unchanged -- the pieces of the row's first `len` tokens concatenated, a run of
+ * S2T_CHRF_SEP (leading and trailing runs included) one break, the reference side renders `unk` through table entry V (unk < 0:
+ * no special rendering), a token outside [0, V) refuses the pair.  Words are the maximal SEP-free runs; there is no punctuation
+ * split here (that is chrF++'s rule).
+ * Units, by `mode`:
+ *   0  words.  A word's unit is the index of its first equal occurrence in the list "hypothesis words, then reference words"
+ *      (lengths and code points compared, no hash): two units of a pair are equal iff the words are.  Units of different pairs do
+ *      not compare.
+ *   1  characters with spaces: the code points of the text with one U+0020 between consecutive words (no leading or trailing one).
+ *   2  characters without spaces: the code points alone.
+ * Operands: hyp [Hrows][Hmax] and ref [Rrows][Rmax], int32 or int64 tokens per side (hyp_elem, ref_elem: 4 or 8), lengths in the
+ * tokens' dtype.  hyp_row / ref_row: int32 [P] or NULL; pair p is row hyp_row[p] against row ref_row[p], NULL means row p (then the
+ * side has P rows).  Nothing is copied or repeated; one matrix may serve both sides.  pieces, piece_off, n_pieces, V, unk: the piece
+ * table, as in s2t_chrf_stats.
+ * Outputs, all int32: hyp_units [P][Uh], ref_units [P][Ur], hyp_n [P], ref_n [P], status [P] (0 done, 2 refused).  Every element of
+ * hyp_n, ref_n and status is written.  hyp_units[p][0 .. hyp_n[p]) and ref_units[p][0 .. ref_n[p]) are written; entries behind them
+ * are not.  A pair is refused -- status 2, hyp_n = ref_n = 0 and nothing else written, beside ordinary pairs that are unaffected --
+ * for a map entry outside its matrix, a length outside [0, padded width], a token outside [0, V) inside a length, offsets of a piece
+ * that descend or leave [0, n_pieces], a side of more than S2T_CHRF_MAX_CHARS characters, or a side with more units than its width
+ * (Uh, Ur; the spaces of mode 1 count).
+ * Kernel: one launch, one pair per workgroup, no atomics, no host read, no memset; a pair's result does not depend on the batch
+ * around it.  The code points are measured, scanned and expanded into LDS by the functions s2t_chrf_stats uses (csrc/text_rows.hpp),
+ * the word starts listed, the units written to global memory.  256 threads for max(Hmax, Rmax) <= S2T_CHRF_GROUP_LEN tokens, 1,024
+ * above.  LDS: two sides of code points and two start lists, 49.2 KB.
+ * Limits: S2T_TEXT_MAX_UNITS units per side (= S2T_EDIT_MAX_B = S2T_CHRF_MAX_CHARS: whatever this call writes, s2t_edit_align
+ * takes) and S2T_CHRF_MAX_LEN tokens of padded width.
+ * Refusals, before anything is launched: S2T_OK at once for P <= 0; S2T_EINVAL for a NULL required pointer (hyp, hyp_len, ref,
+ * ref_len, pieces, piece_off, hyp_units, ref_units, hyp_n, ref_n, status), a negative width, V or n_pieces, an element size other
+ * than 4 or 8, a side without a map whose rows are not P (with one: negative), unk >= V, mode outside [0, 2], Uh or Ur outside
+ * [0, S2T_TEXT_MAX_UNITS]; S2T_ENOTSUP for a token width above S2T_CHRF_MAX_LEN. */
+#define S2T_TEXT_MAX_UNITS 4095
+int s2t_text_units(const void* hyp, const void* hyp_len, int hyp_elem, const void* ref, const void* ref_len, int ref_elem,
+                   const int* hyp_row, const int* ref_row, int P, int Hmax, int Rmax, int Hrows, int Rrows,
+                   const unsigned int* pieces, const int* piece_off, int n_pieces, int V, long long unk, int mode, int Uh, int Ur,
+                   int* hyp_units, int* ref_units, int* hyp_n, int* ref_n, int* status, void* stream);
 /* ---- Kaldi log-mel filterbanks of waveforms (csrc/fbank.hip): torchaudio.compliance.kaldi.fbank with its defaults, restated.
  * Frames: W samples long, S apart, N the next power of two >= W.  An utterance of n samples has m = 0 frames if n < W, else
  * m = 1 + (n - W) / S (snip-edges); frame t is the samples [t*S, t*S + W).  No sample at or behind n is read into a result.
